@@ -2,7 +2,7 @@
 """bench.py -- headline metric of BASELINE.json on MI355X: entities/sec for DAPOL+ tree build + 64-bit range-proof
 generation (one padding-policy inclusion proof per entity, aggregation_factor = height; benches/dapol.rs:59-91,149-175).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--budget-s S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--budget-s S] [--dump-outputs DIR]
       N > 1: one rank per GPU.  Under a launcher (torch.distributed.run sets WORLD_SIZE) this process IS a rank; without one
       the process -- which has not touched the GPU -- starts `python -m torch.distributed.run --nproc-per-node N ... bench.py`
       as a child, relays rank 0's JSON line and exits with the child's code.
@@ -21,11 +21,15 @@ proofs -- at every N: N > 1 is STRONG scaling by default (each GPU owns one top-
 --log2-entities-total 22 gives configs[3] (2^22 over 8); --weak keeps 2^--log2-entities per GPU instead.  The only
 exchange is an all-gather of the N subtree-root records and an all-reduce of the proof checksum.
 
-Wall budget.  One step of configs[2] takes ~19 s, so the driver's `--steps 20 --warmup 5` (25 steps) does not fit its 600 s
-limit with everything else the line carries.  The GPU loop therefore has a wall budget (--budget-s, default 570 s counted from
-process start, including imports / build / context creation and a reserve for the legs after the timed region): after the first warm-up step the number of timed steps is clamped to what fits
-(never below 3) and extra warm-up steps are dropped.  The line reports the steps actually run (`steps`, `warmup`) and
-what was asked for (`steps_requested`, `warmup_requested`).  A heartbeat goes to stderr after every step.
+Steps and wall budget.  Exactly --steps steps are timed, and `ms_per_step` is the wall time of one of them.  One step of
+configs[2] takes ~19 s, so a caller sizes --steps by `ms_per_step`.  The rest of the run has a wall budget (--budget-s,
+default 570 s counted from process start, including imports / build / context creation and a reserve for the legs after the
+timed region): warm-up steps beyond the first two are dropped when they do not fit, and the secondary legs are skipped when
+the budget is spent.  The line reports the steps actually run (`steps`, `warmup`) and what was asked for (`steps_requested`,
+`warmup_requested`).  A heartbeat goes to stderr after every step.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, 64 MB at most): see
+dump_outputs().  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).  Everything in `roofline` outside
 `from_profiles` is measured by THIS run (HIP events on the launch streams inside the library).  The CPU oracle
@@ -236,13 +240,65 @@ def cpu_baseline(generic_lib, height, n_bits, idx, v, r, sample_paths, budget_s=
 
 def plan_steps(steps_req, warm_req, t_step, seconds_left):
     """The wall budget: (further warm-up steps, timed steps) that fit `seconds_left` after the first warm-up step took t_step
-    seconds.  Timed steps are never fewer than min(3, requested); further warm-ups come only out of slack."""
+    seconds.  Timed steps are never fewer than min(3, requested); further warm-ups come only out of slack.  mode_prove takes
+    only the warm-ups from here: it always times --steps steps."""
     if t_step is None or t_step <= 0:
         return 0, steps_req
     fit = int(seconds_left / (t_step * 1.03))
     extra_warm = min(max(0, warm_req - 1), max(0, fit - steps_req))
     steps = min(steps_req, max(min(3, steps_req), fit - extra_warm))
     return extra_warm, steps
+
+
+DUMP_MAX_BYTES = 64 * 10**6      # --dump-outputs: all files together, .npy headers included (64 MB)
+DUMP_SEED = 0xD4902              # the fixed sample of entities dumped when not all of them fit
+
+
+def dump_sample_size(n, height, proof_size, max_bytes=DUMP_MAX_BYTES):
+    """Entities whose inclusion proofs --dump-outputs writes: all n when they fit in max_bytes, else as many as fit.  Per entity:
+    the range proof and the path (8 + 3 x 32 bytes per level) at 4 bytes per byte, and its position (float64); 64 KiB are held
+    back for the root, the checksum and the .npy headers."""
+    per_entity = 4 * (proof_size + height * (8 + 3 * 32)) + 8
+    return int(max(0, min(n, (max_bytes - (64 << 10)) // per_entity)))
+
+
+def _as_f32_bytes(a):
+    """Bytes as float32 (0..255, exact); a uint64 becomes its 8 little-endian bytes on a new last axis."""
+    a = np.asarray(a)
+    if a.dtype == np.uint64:
+        a = a.astype("<u8").reshape(-1).view(np.uint8).reshape(a.shape + (8,))
+    return a.astype(np.float32)
+
+
+def dump_outputs(out_dir, prover, checksum, proof_size):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy per array, float32 holding bytes (a 64-bit
+    integer as its 8 little-endian bytes): the root (root_commitment, root_hash, root_value, root_blinding), the proof-transcript
+    checksum, and for a fixed seeded sample of this rank's entities -- all of them when they fit in DUMP_MAX_BYTES -- their
+    inclusion proofs: `proofs` [s, proof bytes] and the paths, root side first (path_values [s, height, 8], path_blindings,
+    path_commitments, path_hashes [s, height, 32]).  sample_positions (float64) are the entities' positions in the sorted entity
+    list.  Returns what the line says about the dump."""
+    C, H, v, r = prover.root
+    arrays = {"root_commitment": np.frombuffer(C, np.uint8), "root_hash": np.frombuffer(H, np.uint8),
+              "root_value": np.array(v, np.uint64), "root_blinding": np.frombuffer(r, np.uint8), "checksum": np.array(checksum, np.uint64)}
+    n = len(prover.idx) if prover.w is not None else 0
+    s = dump_sample_size(n, prover.height, proof_size)
+    if s:
+        pos = np.arange(n) if s == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=s, replace=False))
+        ids = prover.idx[pos]
+        sv, sr, sC, sH = prover.sample_paths(ids, PAD_SEED, with_nodes=True)
+        arrays.update(proofs=prover.sample_proofs(ids, proof_size), path_values=sv, path_blindings=sr, path_commitments=sC, path_hashes=sH)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, _as_f32_bytes(a))
+        total += os.path.getsize(path)
+    if s:
+        path = os.path.join(out_dir, "sample_positions.npy")
+        np.save(path, pos.astype(np.float64))
+        total += os.path.getsize(path)
+    return {"dir": out_dir, "bytes": total, "entities": s, "entities_of_rank": n,
+            "files": sorted(arrays) + (["sample_positions"] if s else [])}
 
 
 def plan_workload(args, world):
@@ -514,19 +570,16 @@ def mode_prove(args):
         warm_done += 1
         if rank == 0:
             log("warm-up step %d: %.2f s" % (warm_done, t_step))
-    extra_warm, steps = plan_steps(steps_req, warm_req - (warm_done - 1), t_step, deadline - time.time() - post_reserve)
-    if steps < steps_req and world == 1 and not args.no_secondary:
-        # short of time (a slow first `import torch`, a slow box): the requested steps come before the secondary legs, which are
-        # then run only as far as the budget still allows after the timed region
-        lean_reserve = 1.15 * ((args.cpu_budget_s + 4.0 if not args.no_cpu_baseline else 0.0) + 9.0)
-        _, steps = plan_steps(steps_req, 1, t_step, deadline - time.time() - lean_reserve)
-        extra_warm = 0
-    extra_warm, steps = agree_min(extra_warm), agree_min(steps)
+    # --steps is the number of timed steps, whatever the budget: only further warm-ups come out of its slack (and the secondary
+    # legs after the timed region run only as far as the budget still allows)
+    extra_warm, _ = plan_steps(steps_req, warm_req - (warm_done - 1), t_step, deadline - time.time() - post_reserve)
+    steps = steps_req
+    extra_warm = agree_min(extra_warm)
     for _ in range(extra_warm):
         prover.step(PAD_SEED, NONCE_SEED, n_bits)
         warm_done += 1
-    if rank == 0 and (steps != steps_req or warm_done != warm_req):
-        log("wall budget %.0f s: running %d timed steps (asked %d) after %d warm-up (asked %d)" % (args.budget_s, steps, steps_req, warm_done, warm_req))
+    if rank == 0 and warm_done != warm_req:
+        log("wall budget %.0f s: %d warm-up steps (asked %d) before the %d timed steps" % (args.budget_s, warm_done, warm_req, steps))
 
     # ---- timed region: EXACTLY `steps` steps between barrier + synchronize on both sides
     acc = {"tree_ms": 0.0, "prove_ms": 0.0, "msm_ms": 0.0, "msm_launches": 0, "proofs": 0, "mat_ms": 0.0, "mat_launches": 0, "msm_kernels": 0,
@@ -634,6 +687,8 @@ def mode_prove(args):
     if preflight is not None and isinstance(multi_gpu, dict):
         multi_gpu["preflight"] = preflight
 
+    dumped = None                                  # --dump-outputs: what dump_outputs() wrote (set after the headline line)
+
     def make_line(cpu, parity, secondary, complete):
         return {
             "metric": METRIC,
@@ -655,6 +710,7 @@ def mode_prove(args):
             "multi_gpu": multi_gpu,
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "secondary": secondary,
             "checksum": "%016x" % stats.checksum,
+            "outputs_dumped": dumped,
             "complete": complete,
             "wall_s_since_process_start": time.time() - T_PROC0,
         }
@@ -663,6 +719,11 @@ def mode_prove(args):
     # after it, and a run killed at the driver's limit must not lose the line.  The same line is printed again at the end with
     # `cpu_baseline`, `parity` and `secondary` filled in ("complete": true); whoever reads the output takes the LAST line.
     print(json.dumps(make_line(None, None, None, False)), flush=True)
+    if args.dump_outputs:
+        # before the secondary legs run the workload again: the arrays are those of the last timed step
+        dumped = dump_outputs(args.dump_outputs, prover, stats.checksum, int(stats.proof_bytes // max(1, stats.proofs)))
+        log("outputs of the last timed step: %d files, %.1f MB, %d of %d entities, in %s" %
+            (len(dumped["files"]), dumped["bytes"] / 1e6, dumped["entities"], dumped["entities_of_rank"], dumped["dir"]))
     cpu = None
     parity = None
     if not args.no_cpu_baseline and os.path.exists(ORACLE_LIB) and prover.w is not None:
@@ -1419,7 +1480,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mode", choices=("prove", "build", "verify", "criterion"), default="prove")
     ap.add_argument("--budget-s", type=float, default=570.0,
-                    help="wall budget of the whole process, counted from its start; the timed steps are clamped to fit (>= 3)")
+                    help="wall budget of the whole process, counted from its start: extra warm-up steps and the secondary legs run only if they fit "
+                         "(the timed steps are always --steps)")
     ap.add_argument("--cpu-budget-s", type=float, default=10.0, help="wall budget of the CPU-baseline leg")
     ap.add_argument("--no-pinned-leg", action="store_true", help="--mode verify: skip the extra passes from page-locked host buffers (profiling: keeps the kernel counts per pass)")
     ap.add_argument("--no-bad-proof-leg", action="store_true", help="--mode verify: skip the untimed pass with one bad proof (profiling: its per-proof re-check is not part of a pass)")
@@ -1443,7 +1505,14 @@ def main():
                     help="< 30 s, no proving: the library's RCCL communicator up with ncclCommCount == N, the step's two collectives timed, every rank's root equal, rocm-smi --showtopo to stderr")
     ap.add_argument("--preflight-iters", type=int, default=100)
     ap.add_argument("--preflight-timeout-s", type=float, default=30.0, help="deadline of the communicator's creation and of each of its collectives")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB; "
+                         "a fixed seeded sample of the entities when not all fit): see dump_outputs()")
     args = ap.parse_args()
+    if args.dump_outputs is not None:
+        if args.mode != "prove" or args.preflight:
+            raise SystemExit("--dump-outputs applies to the proving workload (--mode prove, no --preflight)")
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus < 1:

@@ -1,8 +1,10 @@
-"""bench.py's host logic that needs no GPU: which workload an (N, flags) pair names, and the wall-budget planner."""
+"""bench.py's host logic that needs no GPU: which workload an (N, flags) pair names, the wall-budget planner, and the files
+--dump-outputs writes."""
 import argparse
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,3 +62,50 @@ def test_no_launcher_means_spawn_not_exit(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     bench.main()
     assert called == {"prove": 1}
+
+
+class _FakeProver:
+    """What dump_outputs() reads of a ShardedProver after a step: the root, the sorted leaf indexes, paths and proofs by leaf."""
+
+    def __init__(self, n, height, proof_size):
+        self.height, self.proof_size, self.w = height, proof_size, object()
+        self.idx = np.arange(n, dtype=np.uint64) * np.uint64(3)
+        self.root = (bytes(range(32)), bytes(range(32, 64)), (1 << 40) + 5, bytes(range(64, 96)))
+
+    def sample_paths(self, leaf_ids, pad_seed, with_nodes=False):
+        b, h = len(leaf_ids), self.height
+        sv = np.repeat(np.asarray(leaf_ids, np.uint64)[:, None], h, axis=1)
+        tag = (np.asarray(leaf_ids) % 251).astype(np.uint8)[:, None, None]
+        sr, sC, sH = (np.broadcast_to(tag + k, (b, h, 32)).copy() for k in (0, 1, 2))
+        return (sv, sr, sC, sH) if with_nodes else (sv, sr)
+
+    def sample_proofs(self, leaf_ids, proof_size):
+        return np.repeat((np.asarray(leaf_ids) % 256).astype(np.uint8)[:, None], proof_size, axis=1)
+
+
+def test_dump_outputs_sample_and_format(tmp_path):
+    """--dump-outputs: float32 bytes (a u64 as its 8 little-endian bytes), every entity when they fit, a fixed seeded sample under
+    64 MB at the headline shape (2^20 entities, height 32, 992-byte proofs), and the same files from run to run."""
+    assert bench.dump_sample_size(1024, 16, 800) == 1024
+    s = bench.dump_sample_size(1 << 20, 32, 992)
+    assert 1000 < s < (1 << 20) and s * (4 * (992 + 32 * 104) + 8) + (64 << 10) <= bench.DUMP_MAX_BYTES
+
+    small = bench.dump_outputs(str(tmp_path / "small"), _FakeProver(100, 8, 64), 0x0102030405060708, 64)
+    assert small["entities"] == 100 and small["bytes"] <= bench.DUMP_MAX_BYTES
+    load = lambda d, name: np.load(os.path.join(d, name + ".npy"))
+    d = small["dir"]
+    for name in small["files"]:
+        assert load(d, name).dtype in (np.float32, np.float64), name
+    assert load(d, "checksum").tolist() == [8, 7, 6, 5, 4, 3, 2, 1]
+    assert load(d, "root_value").tolist() == [5, 0, 0, 0, 0, 1, 0, 0]
+    assert load(d, "root_hash").tolist() == list(range(32, 64))
+    assert load(d, "sample_positions").tolist() == list(range(100))
+    assert load(d, "proofs").shape == (100, 64) and load(d, "path_hashes").shape == (100, 8, 32) and load(d, "path_values").shape == (100, 8, 8)
+    assert load(d, "proofs")[7, 0] == 21 and load(d, "path_values")[7, 3].tolist() == [21, 0, 0, 0, 0, 0, 0, 0]
+
+    big = [bench.dump_outputs(str(tmp_path / k), _FakeProver(1 << 20, 32, 992), 1, 992) for k in ("a", "b")]
+    assert big[0]["entities"] == s and max(b["bytes"] for b in big) <= bench.DUMP_MAX_BYTES
+    pos = load(big[0]["dir"], "sample_positions")
+    assert len(np.unique(pos)) == s and np.all(np.diff(pos) > 0)
+    for name in big[0]["files"]:
+        assert np.array_equal(load(big[0]["dir"], name), load(big[1]["dir"], name)), name
