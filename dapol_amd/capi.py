@@ -84,6 +84,7 @@ _SIG = {
     "dapol_tree_root": (ctypes.c_int32, [_P, _P, _P, _P, _P]),
     "dapol_tree_node_count": (ctypes.c_int32, [_P, _P, _P]),
     "dapol_tree_update": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P]),
+    "dapol_tree_remove": (ctypes.c_int32, [_P, ctypes.c_size_t, _P]),
     "dapol_tree_last_update_path": (ctypes.c_int32, [_P, _P]),
     "dapol_diag_fork_guard_waits": (ctypes.c_int32, [_P]),
     "dapol_diag_verify_fallbacks": (ctypes.c_int32, [_P]),
@@ -623,8 +624,14 @@ class Tree:
         leaf_idx, v, r32 = _u64(leaf_idx), _u64(v), _u8(r32)
         _chk(lib().dapol_tree_update(self.h, leaf_idx.shape[0], _ptr(leaf_idx), _ptr(v), _ptr(r32)))
 
+    def remove(self, leaf_idx):
+        """dapol_tree_remove: drops the leaves at these indexes (all or nothing; the survivors keep their indexes)."""
+        leaf_idx = _u64(leaf_idx)
+        _chk(lib().dapol_tree_remove(self.h, leaf_idx.shape[0], _ptr(leaf_idx)))
+
     def last_update_path(self):
-        """0 = the last update rebuilt the tree, 1 = replaced in place, 2 = inserted in place, 3 = both."""
+        """What the last update or removal did: 0 = rebuilt the tree, 1 = replaced in place, 2 = inserted in place, 3 = both,
+        4 = removed in place."""
         p = ctypes.c_int32(-1)
         _chk(lib().dapol_tree_last_update_path(self.h, ctypes.byref(p)))
         return int(p.value)

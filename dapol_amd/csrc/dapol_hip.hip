@@ -58,7 +58,7 @@ static const char* knob(const char* name) {
     }
     return on ? getenv(name) : nullptr;
 }
-// Fault injection and limit overrides that exist for tests/ only (DAPOL_TEST_FAIL_AFTER_FORK, DAPOL_TEST_FAIL_UPDATE_MIDWAY,
+// Fault injection and limit overrides that exist for tests/ only (DAPOL_TEST_FAIL_AFTER_FORK, DAPOL_TEST_FAIL_UPDATE_MIDWAY / _REMOVE_MIDWAY,
 // DAPOL_LEAF_MAX_TRIES: they make healthy calls fail, or change when DapolError::FailedToMapIndex fires) need a SECOND opt-in,
 // DAPOL_TEST_HOOKS=1, read once per process: the measurement scripts of tools/ export DAPOL_ENV_KNOBS alone and can never trip them,
 // and a call site costs a flag test instead of a getenv + strcmp (round-4 advisor).
@@ -991,6 +991,30 @@ static void level_alt_spans(uint8_t* base, size_t cap, LevelBuf& L, uint64_t** l
     L.parent.p = (uint32_t*)take(cap * 4);
     L.has_pad.p = take(cap);
 }
+// The storage level t moves into when it is rewritten out of place (incremental insert / remove): whichever of its two LevelAlt
+// buffers it does not live in now, grown to hold n_new records.  L (and, for level 0, the leaf pointers) then point into it.
+static hipError_t level_alt_next(dapol_tree_owned* own, int t, size_t n_new, LevelBuf& L, uint64_t** leaf_idx, uint64_t** leaf_v, uint32_t** leaf_r,
+                                 int* which) {
+    auto& A = own->alt[t];
+    const int dstb = A.cur == 0 ? 1 : 0;
+    if (A.cap[dstb] < n_new) {
+        const size_t cap = n_new + 4096 + n_new / 64;
+        hipError_t e = A.buf[dstb].alloc(level_alt_bytes(cap));
+        if (e != hipSuccess) return e;
+        A.cap[dstb] = cap;
+    }
+    level_alt_spans(A.buf[dstb].p, A.cap[dstb], L, leaf_idx, leaf_v, leaf_r, t == 0);
+    L.n = n_new;
+    *which = dstb;
+    return hipSuccess;
+}
+static LevelView level_view_of(const LevelBuf& L, int t, uint64_t* leaf_idx, uint64_t* leaf_v, uint32_t* leaf_r) {
+    LevelView lv;
+    lv.n = L.n;
+    lv.idx = t == 0 ? leaf_idx : L.idx.p; lv.v = t == 0 ? leaf_v : L.v.p; lv.r = t == 0 ? leaf_r : L.r.p;
+    lv.C = L.C.p; lv.H = L.H.p; lv.padC = L.padC.p; lv.padH = L.padH.p; lv.padr = L.padr.p; lv.has_pad = L.has_pad.p; lv.parent = L.parent.p; lv.ext = nullptr;
+    return lv;
+}
 
 // The incremental path for NEW leaves (kernels_ctx_tree.h, "incremental insert"): k sorted, distinct indexes none of which is in the
 // tree.  *done = false and nothing written when two new chains share a node (the caller rebuilds).
@@ -1054,35 +1078,16 @@ static int32_t tree_insert_incremental(dapol_tree_owned* own, size_t k, const st
     uint64_t *n_leaf_idx = own->leaf_idx, *n_leaf_v = own->leaf_v;
     uint32_t* n_leaf_r = own->leaf_r;
     std::vector<int> new_cur((size_t)max_m, -1);
-    for (int t = 0; t < max_m; t++) {
-        auto& A = own->alt[t];
-        const int dstb = A.cur == 0 ? 1 : 0;
-        const size_t n_new = own->levels[t].n + lvl[t].size();
-        if (A.cap[dstb] < n_new) {
-            const size_t cap = n_new + 4096 + n_new / 64;
-            HIPCHK(A.buf[dstb].alloc(level_alt_bytes(cap)));
-            A.cap[dstb] = cap;
-        }
-        level_alt_spans(A.buf[dstb].p, A.cap[dstb], newL[t], &n_leaf_idx, &n_leaf_v, &n_leaf_r, t == 0);
-        newL[t].n = n_new;
-        new_cur[t] = dstb;
-    }
-    auto view_of = [&](const std::vector<LevelBuf>& Ls, int t, uint64_t* li, uint64_t* lv_, uint32_t* lr) {
-        const LevelBuf& L = Ls[t];
-        LevelView lv;
-        lv.n = L.n;
-        lv.idx = t == 0 ? li : L.idx.p; lv.v = t == 0 ? lv_ : L.v.p; lv.r = t == 0 ? lr : L.r.p;
-        lv.C = L.C.p; lv.H = L.H.p; lv.padC = L.padC.p; lv.padH = L.padH.p; lv.padr = L.padr.p; lv.has_pad = L.has_pad.p; lv.parent = L.parent.p; lv.ext = nullptr;
-        return lv;
-    };
+    for (int t = 0; t < max_m; t++)
+        HIPCHK(level_alt_next(own, t, own->levels[t].n + lvl[t].size(), newL[t], &n_leaf_idx, &n_leaf_v, &n_leaf_r, &new_cur[t]));
     const uint32_t* d_lvl = (const uint32_t*)(d + o_lvl);
     for (int t = 0; t < max_m; t++) {
-        LevelView src = view_of(std::vector<LevelBuf>(own->levels.begin(), own->levels.end()), t, own->leaf_idx, own->leaf_v, own->leaf_r);
-        LevelView dst = view_of(newL, t, n_leaf_idx, n_leaf_v, n_leaf_r);
+        LevelView src = level_view_of(own->levels[t], t, own->leaf_idx, own->leaf_v, own->leaf_r);
+        LevelView dst = level_view_of(newL[t], t, n_leaf_idx, n_leaf_v, n_leaf_r);
         const size_t n_old = own->levels[t].n;
         if (n_old)
             hipLaunchKernelGGL(k_tree_relayout, dim3(nblk(n_old, 256)), dim3(256), 0, st, src, dst, n_old, d_lvl + lvl_off[t], (uint32_t)lvl[t].size(),
-                               d_lvl + lvl_off[t + 1], (uint32_t)lvl[t + 1].size(), 0);
+                               d_lvl + lvl_off[t + 1], (uint32_t)lvl[t + 1].size(), 0, RelayoutDel{});
         LAUNCH_CHECK();
     }
     // adopt the new storage, refresh the device-side views
@@ -1117,6 +1122,85 @@ static int32_t tree_insert_incremental(dapol_tree_owned* own, size_t k, const st
     return DAPOL_OK;
 }
 
+// The rebuild paths of dapol_tree_update and dapol_tree_remove: the tree's leaf set comes to the host, the edits are merged into
+// it, and the level-parallel build runs again over the result -- one pass for the whole batch instead of k root-to-leaf walks.
+struct HostLeaves {
+    std::vector<uint64_t> idx, v;
+    std::vector<uint8_t> r;              // [n][32]
+};
+static int32_t tree_host_leaves(dapol_tree* tree, HostLeaves& L) {
+    hipStream_t st = tree->ctx->stream;
+    const size_t n0 = tree->levels[0].n;
+    L.idx.resize(n0); L.v.resize(n0); L.r.resize(n0 * 32);
+    HIPCHK(hipMemcpyAsync(L.idx.data(), tree->leaf_idx, n0 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(L.v.data(), tree->leaf_v, n0 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(L.r.data(), tree->leaf_r, n0 * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return DAPOL_OK;
+}
+// The sorted leaf set `old` with k edits applied, in input order: edit u puts (v[u], r32[u]) at leaf_idx[u] -- inserted, or replacing
+// the leaf there (of several edits of one index the last wins).  v == nullptr: every edit REMOVES the leaf at its index instead
+// (the caller has checked that each one is a leaf; a duplicate removes it once).
+static void merge_leaf_edits(const HostLeaves& old, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32, HostLeaves& out) {
+    const size_t n0 = old.idx.size();
+    const std::vector<uint64_t>& oi = old.idx;
+    std::vector<uint32_t> ord(k);
+    for (size_t i = 0; i < k; i++) ord[i] = (uint32_t)i;
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return leaf_idx[a] < leaf_idx[b]; });
+    std::vector<uint64_t>& ni = out.idx;
+    std::vector<uint64_t>& nv = out.v;
+    std::vector<uint8_t>& nr = out.r;
+    ni.clear(); nv.clear(); nr.clear();
+    ni.reserve(n0 + k); nv.reserve(n0 + k); nr.reserve((n0 + k) * 32);
+    size_t a = 0, b = 0;
+    while (a < n0 || b < k) {
+        if (b < k) {                                        // later updates of the same index win
+            while (b + 1 < k && leaf_idx[ord[b + 1]] == leaf_idx[ord[b]]) b++;
+        }
+        bool take_new = b < k && (a >= n0 || leaf_idx[ord[b]] <= oi[a]);
+        if (take_new) {
+            uint32_t u = ord[b];
+            if (a < n0 && oi[a] == leaf_idx[u]) a++;         // replaces (or removes)
+            if (v) {
+                ni.push_back(leaf_idx[u]); nv.push_back(v[u]);
+                nr.insert(nr.end(), r32 + (size_t)u * 32, r32 + (size_t)u * 32 + 32);
+            }
+            b++;
+        } else {
+            ni.push_back(oi[a]); nv.push_back(old.v[a]);
+            nr.insert(nr.end(), old.r.begin() + a * 32, old.r.begin() + a * 32 + 32);
+            a++;
+        }
+    }
+}
+// Builds the tree again over `L` (sorted, distinct) with its own pad seed and shape, and swaps it in.  An error leaves the old tree.
+static int32_t tree_rebuild(dapol_tree_owned* own, const HostLeaves& L) {
+    dapol_ctx* ctx = own->ctx;
+    hipStream_t st = ctx->stream;
+    const size_t n = L.idx.size();
+    if (n > ((size_t)1 << 31)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "at most 2^31 leaves per GPU (32-bit node positions); memory is the practical bound");
+    dapol_tree_owned fresh;
+    HIPCHK(fresh.leaves.idx.alloc(n)); HIPCHK(fresh.leaves.v.alloc(n)); HIPCHK(fresh.leaves.r.alloc(n * 8));
+    HIPCHK(hipMemcpyAsync(fresh.leaves.idx.p, L.idx.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(fresh.leaves.v.p, L.v.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(fresh.leaves.r.p, L.r.data(), n * 32, hipMemcpyHostToDevice, st));
+    uint8_t seed[32];
+    memcpy(seed, own->pad_seed, 32);
+    int32_t rc = tree_build_device(ctx, own->index_bits, own->shard_bits, n, fresh.leaves.idx.p, fresh.leaves.v.p, fresh.leaves.r.p, seed, &fresh);
+    if (rc != DAPOL_OK) return rc;
+    fresh.holds_ctx = own->holds_ctx;
+    *own = std::move(fresh);
+    return DAPOL_OK;
+}
+// dapol_options::update_incremental_max as the in-place paths read it (0 = none in place).
+static size_t incremental_max(const dapol_ctx* ctx) {
+    size_t inc_max = 65536;
+    if (ctx->opt.update_incremental_max > 0) inc_max = (size_t)ctx->opt.update_incremental_max;
+    if (ctx->opt.update_incremental_max < 0) inc_max = 0;
+    if (const char* e = knob("DAPOL_UPDATE_INCREMENTAL_MAX")) inc_max = (size_t)atoll(e);
+    return inc_max;
+}
+
 static int32_t tree_update_impl(dapol_tree* tree, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32);
 int32_t dapol_tree_update(dapol_tree* tree, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32) {
     int32_t rc = tree_update_impl(tree, k, leaf_idx, v, r32);
@@ -1141,10 +1225,7 @@ static int32_t tree_update_impl(dapol_tree* tree, size_t k, const uint64_t* leaf
     // structure: up to DAPOL_UPDATE_INCREMENTAL_MAX (default 65,536, and at most an eighth of the leaves) such updates are applied
     // in place on the device.  Anything else -- a new index, a big batch -- takes the rebuild below, which is bit for bit the same tree.
     {
-        size_t inc_max = 65536;
-        if (ctx->opt.update_incremental_max > 0) inc_max = (size_t)ctx->opt.update_incremental_max;
-        if (ctx->opt.update_incremental_max < 0) inc_max = 0;
-        if (const char* e = knob("DAPOL_UPDATE_INCREMENTAL_MAX")) inc_max = (size_t)atoll(e);
+        const size_t inc_max = incremental_max(ctx);
         if (k <= inc_max && k <= tree->levels[0].n / 8 + 1 && tree->levels[0].n > 0) {
             std::vector<uint32_t> ord(k);
             for (size_t i = 0; i < k; i++) ord[i] = (uint32_t)i;
@@ -1198,58 +1279,196 @@ static int32_t tree_update_impl(dapol_tree* tree, size_t k, const uint64_t* leaf
             }
         }
     }
-    const size_t n0 = tree->levels[0].n;
-    std::vector<uint64_t> oi(n0), ov(n0);
-    std::vector<uint8_t> orr(n0 * 32);
-    HIPCHK(hipMemcpyAsync(oi.data(), tree->leaf_idx, n0 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(ov.data(), tree->leaf_v, n0 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(orr.data(), tree->leaf_r, n0 * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<uint32_t> ord(k);
-    for (size_t i = 0; i < k; i++) ord[i] = (uint32_t)i;
-    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return leaf_idx[a] < leaf_idx[b]; });
-    std::vector<uint64_t> ni, nv;
-    std::vector<uint8_t> nr;
-    ni.reserve(n0 + k); nv.reserve(n0 + k); nr.reserve((n0 + k) * 32);
-    size_t a = 0, b = 0;
-    while (a < n0 || b < k) {
-        if (b < k) {                                        // later updates of the same index win
-            while (b + 1 < k && leaf_idx[ord[b + 1]] == leaf_idx[ord[b]]) b++;
-        }
-        bool take_new = b < k && (a >= n0 || leaf_idx[ord[b]] <= oi[a]);
-        if (take_new) {
-            uint32_t u = ord[b];
-            if (a < n0 && oi[a] == leaf_idx[u]) a++;         // replaces
-            ni.push_back(leaf_idx[u]); nv.push_back(v[u]);
-            nr.insert(nr.end(), r32 + (size_t)u * 32, r32 + (size_t)u * 32 + 32);
-            b++;
-        } else {
-            ni.push_back(oi[a]); nv.push_back(ov[a]);
-            nr.insert(nr.end(), orr.begin() + a * 32, orr.begin() + a * 32 + 32);
-            a++;
-        }
-    }
-    const size_t n = ni.size();
-    if (n > ((size_t)1 << 31)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "at most 2^31 leaves per GPU (32-bit node positions); memory is the practical bound");
-    dapol_tree_owned fresh;
-    HIPCHK(fresh.leaves.idx.alloc(n)); HIPCHK(fresh.leaves.v.alloc(n)); HIPCHK(fresh.leaves.r.alloc(n * 8));
-    HIPCHK(hipMemcpyAsync(fresh.leaves.idx.p, ni.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(fresh.leaves.v.p, nv.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(fresh.leaves.r.p, nr.data(), n * 32, hipMemcpyHostToDevice, st));
-    uint8_t seed[32];
-    memcpy(seed, tree->pad_seed, 32);
-    int32_t rc = tree_build_device(ctx, tree->index_bits, tree->shard_bits, n, fresh.leaves.idx.p, fresh.leaves.v.p, fresh.leaves.r.p, seed, &fresh);
+    HostLeaves old, cur;
+    int32_t rc = tree_host_leaves(tree, old);
+    if (rc != DAPOL_OK) return rc;
+    merge_leaf_edits(old, k, leaf_idx, v, r32, cur);
+    rc = tree_rebuild(own, cur);
     if (rc != DAPOL_OK) return rc;                          // the old tree stays as it was
-    fresh.holds_ctx = own->holds_ctx;
-    *own = std::move(fresh);
     own->last_update_path = 0;
     return DAPOL_OK;
 }
-// What the last dapol_tree_update on this tree did: 0 = rebuilt the tree, 1 = replaced existing leaves in place, 2 = inserted new
-// leaves in place, 3 = both.  (Diagnostics: the result is the same tree whichever path ran.)
+// What the last dapol_tree_update / dapol_tree_remove on this tree did: 0 = rebuilt the tree, 1 = replaced existing leaves in place,
+// 2 = inserted new leaves in place, 3 = both, 4 = removed leaves in place.  (Diagnostics: the result is the same tree whichever path ran.)
 int32_t dapol_tree_last_update_path(dapol_tree* tree, int32_t* path) {
     if (!tree || !path) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
     *path = static_cast<dapol_tree_owned*>(tree)->last_update_path;
+    return DAPOL_OK;
+}
+
+// The in-place path of dapol_tree_remove (kernels_ctx_tree.h, "incremental remove"); si = the indexes, sorted and distinct.  An index
+// that is not a leaf (DAPOL_ERR_UNKNOWN_LEAF) or a batch that holds every leaf (DAPOL_ERR_INVALID_ARGUMENT) is reported before anything
+// has been written.
+static int32_t tree_remove_incremental(dapol_tree_owned* own, const std::vector<uint64_t>& si) {
+    dapol_ctx* ctx = own->ctx;
+    hipStream_t st = ctx->stream;
+    const int H = own->height;
+    const size_t k = si.size(), S1 = (size_t)H + 1;
+    // R0: idx | pos | has_pad | missing
+    {
+        const size_t o_pos = k * 8, o_hp = o_pos + k * S1 * 4, o_miss = align_up(o_hp + k * S1, 8), total = o_miss + 8;
+        if (own->upd_scratch.n < total) HIPCHK(own->upd_scratch.alloc(total + total / 2));
+    }
+    const size_t o_pos = k * 8, o_hp = o_pos + k * S1 * 4, o_miss = align_up(o_hp + k * S1, 8);
+    uint8_t* d = own->upd_scratch.p;
+    HIPCHK(hipMemcpyAsync(d, si.data(), k * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d + o_miss, 0, 8, st));
+    TreeRmFind F{k, H, (const uint64_t*)d, (uint32_t*)(d + o_pos), d + o_hp, (uint32_t*)(d + o_miss)};
+    hipLaunchKernelGGL(k_tree_rm_find, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, F);
+    LAUNCH_CHECK();
+    uint32_t missing = 0;
+    HIPCHK(hipMemcpyAsync(&missing, d + o_miss, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (missing) return fail(DAPOL_ERR_UNKNOWN_LEAF, "an index to remove is not a leaf of the tree (nothing was removed)");
+    if (k >= own->levels[0].n) return fail(DAPOL_ERR_INVALID_ARGUMENT, "removing every leaf would leave an empty tree (nothing was removed)");
+    std::vector<uint32_t> pos(k * S1);
+    std::vector<uint8_t> hp(k * S1);
+    HIPCHK(hipMemcpyAsync(pos.data(), d + o_pos, k * S1 * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hp.data(), d + o_hp, k * S1, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // The plan, level by level, in the old layout.  The touched nodes of level t are the distinct pos[j][t] in order (the leaves are
+    // sorted, so are their ancestors' positions); rep = the first removed leaf under the node.  A parent has one or two touched children.
+    struct Node { uint32_t pos, rep; bool dead; };
+    std::vector<std::vector<uint32_t>> dead(S1), merge(S1);      // merge[t]: (survivor at t, one of its surviving children at t - 1)
+    std::vector<uint32_t> pad_pos;                                 // chain tops: the surviving sibling S (level pad_lvl)
+    std::vector<uint8_t> pad_lvl;
+    std::vector<Node> cur, nxt;
+    for (size_t j = 0; j < k; j++) { cur.push_back({pos[j * S1], (uint32_t)j, true}); dead[0].push_back(pos[j * S1]); }
+    for (int t = 0; t < H; t++) {
+        nxt.clear();
+        for (size_t a = 0; a < cur.size();) {
+            const uint32_t par = pos[cur[a].rep * S1 + t + 1];
+            size_t b = a + 1;
+            while (b < cur.size() && pos[cur[b].rep * S1 + t + 1] == par) b++;
+            const Node c0 = cur[a];
+            bool pdead, top = false;
+            uint32_t child = 0;                                    // a surviving child of a surviving parent
+            if (b - a == 2) {                                      // both children touched
+                const Node c1 = cur[a + 1];
+                pdead = c0.dead && c1.dead;
+                child = c0.dead ? c1.pos : c0.pos;
+                top = c0.dead != c1.dead;
+            } else {
+                pdead = c0.dead && hp[c0.rep * S1 + t];            // a node with has_pad has one real child
+                top = c0.dead && !pdead;
+                child = !top ? c0.pos : ((si[c0.rep] >> t) & 1) ? c0.pos - 1 : c0.pos + 1;     // S: the real neighbour
+            }
+            if (top) { pad_lvl.push_back((uint8_t)t); pad_pos.push_back(child); }
+            if (pdead) dead[t + 1].push_back(par);
+            else { merge[t + 1].push_back(par); merge[t + 1].push_back(child); }
+            nxt.push_back({par, c0.rep, pdead});
+            a = b;
+        }
+        std::swap(cur, nxt);
+    }
+    if (!dead[H].empty()) return fail(DAPOL_ERR_INVALID_ARGUMENT, "internal: the root of a tree with leaves left died");
+    int D = 0;                                                     // levels 0 .. D - 1 lose nodes
+    while (D < H && !dead[D].empty()) D++;
+    // old -> new positions: minus the deletions before
+    auto newpos = [&](int t, uint32_t o) { return o - (uint32_t)(std::lower_bound(dead[t].begin(), dead[t].end(), o) - dead[t].begin()); };
+    for (size_t i = 0; i < pad_pos.size(); i++) pad_pos[i] = newpos(pad_lvl[i], pad_pos[i]);
+    for (int t = 1; t <= H; t++)
+        for (size_t i = 0; i < merge[t].size(); i += 2) { merge[t][i] = newpos(t, merge[t][i]); merge[t][i + 1] = newpos(t - 1, merge[t][i + 1]); }
+    // one upload: pad seed | dead lists | pad positions | merge pairs | pad levels
+    std::vector<uint32_t> flat(8);
+    memcpy(flat.data(), own->pad_seed, 32);
+    std::vector<size_t> dead_off(S1 + 1), merge_off(S1 + 1);
+    for (size_t t = 0; t <= S1; t++) { dead_off[t] = flat.size(); if (t < S1) flat.insert(flat.end(), dead[t].begin(), dead[t].end()); }
+    const size_t pad_off = flat.size();
+    flat.insert(flat.end(), pad_pos.begin(), pad_pos.end());
+    for (size_t t = 0; t <= S1; t++) { merge_off[t] = flat.size(); if (t < S1) flat.insert(flat.end(), merge[t].begin(), merge[t].end()); }
+    const size_t o_lvl = flat.size() * 4, total = o_lvl + pad_lvl.size();
+    if (own->upd_scratch.n < total) HIPCHK(own->upd_scratch.alloc(total + total / 2));
+    d = own->upd_scratch.p;
+    const uint32_t* dw = (const uint32_t*)d;
+    HIPCHK(hipMemcpyAsync(d, flat.data(), o_lvl, hipMemcpyHostToDevice, st));
+    if (!pad_lvl.empty()) HIPCHK(hipMemcpyAsync(d + o_lvl, pad_lvl.data(), pad_lvl.size(), hipMemcpyHostToDevice, st));
+    // R1: the levels that lose nodes, compacted into storage of their own (the tree's arrays are not touched yet)
+    if (own->alt.size() != own->levels.size()) own->alt.resize(own->levels.size());
+    std::vector<LevelBuf> newL(own->levels.begin(), own->levels.end());
+    uint64_t *n_leaf_idx = own->leaf_idx, *n_leaf_v = own->leaf_v;
+    uint32_t* n_leaf_r = own->leaf_r;
+    std::vector<int> new_cur((size_t)D, -1);
+    for (int t = 0; t < D; t++)
+        HIPCHK(level_alt_next(own, t, own->levels[t].n - dead[t].size(), newL[t], &n_leaf_idx, &n_leaf_v, &n_leaf_r, &new_cur[t]));
+    for (int t = 0; t < D; t++) {
+        LevelView src = level_view_of(own->levels[t], t, own->leaf_idx, own->leaf_v, own->leaf_r);
+        LevelView dst = level_view_of(newL[t], t, n_leaf_idx, n_leaf_v, n_leaf_r);
+        const size_t n_old = own->levels[t].n;
+        const RelayoutDel del{dw + dead_off[t], (uint32_t)dead[t].size(), dw + dead_off[t + 1], (uint32_t)dead[t + 1].size()};
+        hipLaunchKernelGGL(k_tree_relayout, dim3(nblk(n_old, 256)), dim3(256), 0, st, src, dst, n_old, (const uint32_t*)nullptr, 0u,
+                           (const uint32_t*)nullptr, 0u, 0, del);
+        LAUNCH_CHECK();
+    }
+    TreePoison poison{own, true};                            // the tree's own state changes from here on
+    if (test_knob("DAPOL_TEST_FAIL_REMOVE_MIDWAY")) return fail(DAPOL_ERR_HIP, "injected failure between the compaction and the re-merge (test knob)");
+    for (int t = 0; t < D; t++) { own->levels[t] = newL[t]; own->alt[t].cur = new_cur[t]; }
+    own->leaf_idx = n_leaf_idx; own->leaf_v = n_leaf_v; own->leaf_r = n_leaf_r;
+    std::vector<LevelView> hv(S1);
+    for (int t = 0; t <= H; t++) hv[t] = own->view(t, nullptr);
+    HIPCHK(hipMemcpyAsync(own->d_views.p, hv.data(), hv.size() * sizeof(LevelView), hipMemcpyHostToDevice, st));
+    // R2: the chain tops' siblings take their padding nodes; R3: the touched survivors, bottom-up
+    if (!pad_pos.empty()) {
+        hipLaunchKernelGGL(k_tree_rm_pad, dim3(nblk(pad_pos.size(), 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, pad_pos.size(), d + o_lvl,
+                           dw + pad_off, dw);
+        LAUNCH_CHECK();
+    }
+    for (int t = 0; t < H; t++) {
+        const size_t n = merge[t + 1].size() / 2;
+        if (!n) continue;
+        hipLaunchKernelGGL(k_tree_rm_merge, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + merge_off[t + 1]);
+        LAUNCH_CHECK();
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    own->n_real = 0;
+    own->n_pad = 0;
+    for (int t = 0; t <= H; t++) {
+        own->n_real += own->levels[t].n;
+        if (t < H) own->n_pad += 2 * (uint64_t)own->levels[t + 1].n - own->levels[t].n;
+    }
+    poison.armed = false;
+    return DAPOL_OK;
+}
+
+static int32_t tree_remove_impl(dapol_tree* tree, size_t k, const uint64_t* leaf_idx);
+int32_t dapol_tree_remove(dapol_tree* tree, size_t k, const uint64_t* leaf_idx) {
+    int32_t rc = tree_remove_impl(tree, k, leaf_idx);
+    if (rc || !tree || !k || !ctx_wide(tree->ctx)) return rc;
+    // a 64-byte digest: lay the whole 64-byte chain again, as dapol_tree_update does
+    rc = tree_hash_wide(tree);
+    if (rc) tree->invalid = true;
+    return rc;
+}
+static int32_t tree_remove_impl(dapol_tree* tree, size_t k, const uint64_t* leaf_idx) {
+    if (!tree || (k && !leaf_idx)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return DAPOL_OK;
+    TREE_USABLE(tree);
+    if (tree->tape_built) return fail(DAPOL_ERR_INVALID_ARGUMENT, "the tree was built from a padding tape: a removal may need draws the tape does not hold; build it again");
+    dapol_tree_owned* own = static_cast<dapol_tree_owned*>(tree);
+    if (!own->leaves.idx.p) return fail(DAPOL_ERR_INVALID_ARGUMENT, "tree does not own its leaves (workload tree): rebuild the workload instead");
+    dapol_ctx* ctx = tree->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<uint64_t> si(leaf_idx, leaf_idx + k);
+    std::sort(si.begin(), si.end());
+    si.erase(std::unique(si.begin(), si.end()), si.end());
+    // In place up to update_incremental_max removals (and at most an eighth of the leaves), as dapol_tree_update; otherwise the
+    // surviving leaves are built again, which is bit for bit the same tree.
+    if (tree->height >= 1 && si.size() <= incremental_max(ctx) && si.size() <= tree->levels[0].n / 8 + 1) {
+        int32_t rc = tree_remove_incremental(own, si);
+        if (rc != DAPOL_OK) return rc;
+        own->last_update_path = 4;
+        return DAPOL_OK;
+    }
+    HostLeaves old, cur;
+    int32_t rc = tree_host_leaves(tree, old);
+    if (rc != DAPOL_OK) return rc;
+    for (uint64_t x : si)
+        if (!std::binary_search(old.idx.begin(), old.idx.end(), x)) return fail(DAPOL_ERR_UNKNOWN_LEAF, "an index to remove is not a leaf of the tree (nothing was removed)");
+    if (si.size() >= old.idx.size()) return fail(DAPOL_ERR_INVALID_ARGUMENT, "removing every leaf would leave an empty tree (nothing was removed)");
+    merge_leaf_edits(old, si.size(), si.data(), nullptr, nullptr, cur);
+    rc = tree_rebuild(own, cur);
+    if (rc != DAPOL_OK) return rc;                          // the old tree stays as it was
+    own->last_update_path = 0;
     return DAPOL_OK;
 }
 

@@ -549,17 +549,25 @@ __global__ __launch_bounds__(64) void k_tree_ins_plan(const LevelView* views, Tr
     }
 }
 // Existing nodes of one level to their new positions.  ins_pos: sorted old-layout lower-bound positions of the nodes this level
-// gains (n_ins of them); next_ins_pos / n_next: the same for the level above (parent pointers move with it).
+// gains (n_ins of them); next_ins_pos / n_next: the same for the level above (parent pointers move with it).  The removal path
+// (below) passes the level's deleted positions instead: del_pos / n_del, sorted and distinct, old layout; those nodes are dropped
+// and the others move down by the number of deletions before them; next_del_pos / n_next_del: the same for the level above.
 __device__ __forceinline__ uint32_t count_le(const uint32_t* a, uint32_t n, uint32_t x) {      // # of a[i] <= x, a sorted
     uint32_t lo = 0, hi = n;
     while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (a[mid] <= x) lo = mid + 1; else hi = mid; }
     return lo;
 }
+struct RelayoutDel {
+    const uint32_t* pos; uint32_t n;               // deleted positions of this level
+    const uint32_t* next_pos; uint32_t n_next;     // of the level above
+};
 __global__ __launch_bounds__(256) void k_tree_relayout(LevelView src, LevelView dst, size_t n_old, const uint32_t* ins_pos, uint32_t n_ins,
-                                                       const uint32_t* next_ins_pos, uint32_t n_next, int is_root_level) {
+                                                       const uint32_t* next_ins_pos, uint32_t n_next, int is_root_level, RelayoutDel del) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_old) return;
-    const size_t d = i + count_le(ins_pos, n_ins, (uint32_t)i);
+    const uint32_t dl = del.n ? count_le(del.pos, del.n, (uint32_t)i) : 0u;
+    if (dl && del.pos[dl - 1] == (uint32_t)i) return;                   // a deleted node
+    const size_t d = i + count_le(ins_pos, n_ins, (uint32_t)i) - dl;
     dst.idx[d] = src.idx[i];
     dst.v[d] = src.v[i];
     uint32_t w[8];
@@ -574,7 +582,7 @@ __global__ __launch_bounds__(256) void k_tree_relayout(LevelView src, LevelView 
     }
     if (!is_root_level) {
         const uint32_t pq = src.parent[i];
-        dst.parent[d] = pq + (n_next ? count_le(next_ins_pos, n_next, pq) : 0u);
+        dst.parent[d] = pq + (n_next ? count_le(next_ins_pos, n_next, pq) : 0u) - (del.n_next ? count_le(del.next_pos, del.n_next, pq) : 0u);
     }
 }
 struct TreeInsArgs {
@@ -682,6 +690,108 @@ __global__ __launch_bounds__(64) void k_tree_ins_chain(TableView tbl, const Leve
         pos[m] = (uint32_t)p;
         for (int q = m; q < I.height; q++) { p = views[q].parent[p]; pos[q + 1] = (uint32_t)p; }
     }
+}
+
+// ------------------------------------------------------------------------------------- incremental remove
+// Removing leaves (dapol_tree_remove) is the mirror image of the insert.  A real node dies iff all its real children die (a node
+// whose has_pad is set has one real child); the dead nodes of a removed leaf form a chain from the leaf up to a CHAIN TOP whose
+// parent survives.  That parent had two real children, so the top's sibling S survives: S gains has_pad and the padding node of
+// the top's position (level t, idx_S ^ 1) -- the very draw k_tree_pad_level makes for it.  Padding records of dead nodes go with
+// them; a survivor never loses has_pad.  Chains may share nodes (two sibling leaves, a whole subtree): the host finds the dead
+// nodes and the touched survivors level by level from R0's positions, and every touched survivor is merged again from its children.
+//   R0  k_tree_rm_find     per removed leaf: its node position and has_pad flag at every level (parent pointers); a missing index
+//                          reports DAPOL_ERR_UNKNOWN_LEAF before anything has been written
+//   R1  k_tree_relayout    per level that loses nodes: the survivors, compacted (with the deletions of RelayoutDel)
+//   R2  k_tree_rm_pad      per chain top: S's new padding sibling
+//   R3  k_tree_rm_merge    per level, bottom-up: every touched survivor = Mergeable::merge of its children, as k_tree_merge makes it
+// A survivor is re-merged rather than moved by a delta: the parent of a chain top may also change through removals under S, and
+// chain tops sit at different levels, so the deltas of one ancestor would have to be gathered across chains; a merge reads what
+// is already there (children of the level below, the padding records of R2) and needs no bookkeeping between chains.
+struct TreeRmFind {
+    size_t k;
+    int height;
+    const uint64_t* idx;       // [k] sorted, distinct
+    uint32_t* pos;             // [k][height + 1] node position at every level (old layout)
+    uint8_t* has_pad;          // [k][height + 1] has_pad of that node
+    uint32_t* missing;         // != 0: some index is not a leaf of the tree
+};
+__global__ __launch_bounds__(64) void k_tree_rm_find(const LevelView* views, TreeRmFind F) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= F.k) return;
+    const LevelView L0 = views[0];
+    const uint64_t want = F.idx[j];
+    size_t lo = 0, hi = L0.n;
+    while (lo < hi) {
+        const size_t mid = (lo + hi) >> 1;
+        if (L0.idx[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= L0.n || L0.idx[lo] != want) { atomicOr(F.missing, 1u); return; }
+    const size_t stride = (size_t)F.height + 1;
+    uint32_t* pos = F.pos + j * stride;
+    uint8_t* hp = F.has_pad + j * stride;
+    size_t p = lo;
+    for (int t = 0; t < F.height; t++) { pos[t] = (uint32_t)p; hp[t] = views[t].has_pad[p]; p = views[t].parent[p]; }
+    pos[F.height] = (uint32_t)p;
+    hp[F.height] = 0;
+}
+// R2: one lane per chain top; level[i] / pos[i] = level and (new) position of the surviving sibling S.
+__global__ __launch_bounds__(64) void k_tree_rm_pad(TableView tbl, const LevelView* views, size_t n, const uint8_t* level, const uint32_t* pos,
+                                                    const uint32_t* pad_seed) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int t = level[i];
+    const size_t s = pos[i];
+    const LevelView L = views[t];
+    uint32_t seed[8], wide[16], rB[8], cB[8], hB[8];
+    for (int k = 0; k < 8; k++) seed[k] = pad_seed[k];
+    seed_wide(wide, seed, 1u, (uint64_t)t, L.idx[s] ^ 1ull);
+    sc rm;
+    sc_from_wide(rm, wide);
+    sc_from_mont(rB, rm);
+    ge_p3 pB;
+    ge_identity(pB);
+    tbl_fixed_mul_add(pB, tbl, tbl.row_Bb(0), rB);
+    ge_compress(cB, pB);
+    node_hash32(tbl.digest, hB, cB);
+    st8(L.padC + s * 8, cB);
+    st8(L.padH + s * 8, hB);
+    st8(L.padr + s * 8, rB);
+    L.has_pad[s] = 1;
+}
+// R3, one level: pc[2 i] = position of a touched survivor in nxt, pc[2 i + 1] = position of one of its surviving children in cur
+// (new layout).  The other child is the padding record of that child or its real neighbour, as k_tree_merge pairs them.
+__global__ __launch_bounds__(64) void k_tree_rm_merge(int digest, LevelView cur, LevelView nxt, size_t n, const uint32_t* pc) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const size_t p = pc[2 * i], c = pc[2 * i + 1];
+    const bool left = (cur.idx[c] & 1ull) == 0;
+    uint32_t cA[8], hA[8], rA[8], cB[8], hB[8], rB[8];
+    const uint64_t vA = cur.v[c];
+    uint64_t vB = 0;
+    ld8(cA, cur.C + c * 8); ld8(hA, cur.H + c * 8); ld8(rA, cur.r + c * 8);
+    if (cur.has_pad[c]) { ld8(cB, cur.padC + c * 8); ld8(hB, cur.padH + c * 8); ld8(rB, cur.padr + c * 8); }
+    else {
+        const size_t s = left ? c + 1 : c - 1;
+        ld8(cB, cur.C + s * 8); ld8(hB, cur.H + s * 8); ld8(rB, cur.r + s * 8);
+        vB = cur.v[s];
+    }
+    ge_p3 pA, pB, pp;
+    (void)ge_decompress(pA, cA);                   // the tree's own encodings: always decode
+    (void)ge_decompress(pB, cB);
+    ge_add(pp, pA, pB);
+    sc ma, mb, ms;
+    sc_to_mont(ma, rA);
+    sc_to_mont(mb, rB);
+    sc_add(ms, ma, mb);
+    uint32_t rp[8], cp[8], hp[8];
+    sc_from_mont(rp, ms);
+    ge_compress(cp, pp);
+    if (left) node_hash128(digest, hp, cA, cB, hA, hB);
+    else node_hash128(digest, hp, cB, cA, hB, hA);
+    nxt.v[p] = vA + vB;                            // u64 wrap == release-mode Rust (node.rs:72)
+    st8(nxt.r + p * 8, rp);
+    st8(nxt.C + p * 8, cp);
+    st8(nxt.H + p * 8, hp);
 }
 
 // ------------------------------------------------------------------------------------- small trees, by phases

@@ -346,6 +346,26 @@ class Dapol {
         }
         check(dapol_tree_update(tree_.get(), idx.size(), idx.data(), values.data(), blindings[0].data()));
     }
+    // Removes the liabilities at these leaf indexes (dapol_tree_remove; the crate has no removal): all or nothing, the survivors keep
+    // their indexes, and the tree equals a build over the survivors with the same seed.  An index that is not a leaf throws
+    // DapolError(DAPOL_ERR_UNKNOWN_LEAF); removing every leaf throws DapolError(DAPOL_ERR_INVALID_ARGUMENT).
+    void remove(const std::vector<uint64_t>& idx) {
+        if (idx.empty()) return;
+        if (!tree_) throw DapolError(DAPOL_ERR_UNKNOWN_LEAF);
+        check(dapol_tree_remove(tree_.get(), idx.size(), idx.data()));
+    }
+    // The same by internal id; the ids leave id_to_idx_map() too.  An unknown id throws DapolError(DAPOL_ERR_UNKNOWN_LEAF) with
+    // nothing removed.
+    void remove_ids(const std::vector<LiabilityId>& ids) {
+        std::vector<uint64_t> idx;
+        for (auto& id : ids) {
+            auto it = id_to_idx_map_.find(id);
+            if (it == id_to_idx_map_.end()) throw DapolError(DAPOL_ERR_UNKNOWN_LEAF);
+            idx.push_back(it->second);
+        }
+        remove(idx);
+        for (auto& id : ids) id_to_idx_map_.erase(id);
+    }
     // Dapol::root_raw / Dapol::root (mod.rs:134-141)
     DapolNode root_raw() const {
         DapolNode n;

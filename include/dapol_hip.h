@@ -107,7 +107,8 @@ typedef struct {
                                          takes over earlier (see generator_stationary; it yields only to generator_stationary = -1).  An explicit value is
                                          taken as it is for proofs of >= 1,024 generators a side */
     int32_t verify_batch_min;         /* fewest proofs the verifier checks as ONE random linear combination (0: 112) */
-    int64_t update_incremental_max;   /* dapol_tree_update: most replaced leaves re-merged in place (0: 65,536; -1: always rebuild) */
+    int64_t update_incremental_max;   /* dapol_tree_update / dapol_tree_remove: most leaves replaced, inserted or removed in place, and never more
+                                         than an eighth of the tree's leaves (0: 65,536; -1: always rebuild) */
     int32_t gs_slices;                /* slices of a list swept side by side by the generator-stationary MSM: 1, 2, 4, 8, 16 (0: as many as fill the chip) */
     int32_t profile;                  /* creation: DAPOL_PROFILE_BENCH (0, the default) or DAPOL_PROFILE_HOST: the defaults of the memory fields above.
                                          BENCH spends HBM for the last percent of throughput: 17-bit windows + high-half rows (69 GB of tables for 32
@@ -207,8 +208,17 @@ int32_t dapol_tree_destroy(dapol_tree* tree);
  * On a context with a 64-byte digest the whole hash chain is laid again after the update; a tree built from a padding tape
  * (dapol_tree_build_tape) cannot be updated. */
 int32_t dapol_tree_update(dapol_tree* tree, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32);
-/* What the last dapol_tree_update on this tree did: 0 = rebuilt, 1 = replaced existing leaves in place, 2 = inserted new leaves in
- * place, 3 = both (diagnostics; the tree is the same whichever path ran). */
+/* Removes the k leaves at leaf_idx (in any order; a duplicate removes its leaf once; k = 0 does nothing).  Surviving leaves keep their
+ * indexes, and afterwards the tree equals dapol_tree_build (dapol_tree_build_shard) over the remaining leaves with the tree's pad
+ * seed bit for bit, at every level.  All or nothing: an index that is not a leaf of the tree (also one outside the tree or outside a
+ * shard's prefix) -> DAPOL_ERR_UNKNOWN_LEAF, a batch that holds every leaf -> DAPOL_ERR_INVALID_ARGUMENT, both with the tree
+ * unchanged.  Refused like dapol_tree_update: trees built from a padding tape, workload trees, trees marked invalid.  Batches within
+ * update_incremental_max (dapol_options) and at most an eighth of the leaves are removed IN PLACE on the device; a HIP failure
+ * between the first and the last write of such a removal marks the tree invalid, as for dapol_tree_update.  Larger batches rebuild
+ * the tree from the surviving leaves (an error then leaves the old tree as it was). */
+int32_t dapol_tree_remove(dapol_tree* tree, size_t k, const uint64_t* leaf_idx);
+/* What the last dapol_tree_update / dapol_tree_remove on this tree did: 0 = rebuilt, 1 = replaced existing leaves in place, 2 = inserted
+ * new leaves in place, 3 = both, 4 = removed leaves in place (diagnostics; the tree is the same whichever path ran). */
 int32_t dapol_tree_last_update_path(dapol_tree* tree, int32_t* path);
 /* Dapol::root_raw / Dapol::root (src/dapol/mod.rs:134-141). Any out pointer may be NULL. */
 int32_t dapol_tree_root(dapol_tree* tree, uint8_t C32[32], uint8_t H32[32], uint64_t* v, uint8_t r32[32]);
