@@ -2,7 +2,10 @@
 """bench.py -- headline metric of BASELINE.json on MI355X: entities/sec for DAPOL+ tree build + 64-bit range-proof
 generation (one padding-policy inclusion proof per entity, aggregation_factor = height; benches/dapol.rs:59-91,149-175).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--budget-s S] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--budget-s S] [--dump-outputs DIR] [--full]
+      A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, one JSON line.  --full
+      adds the legs after the timed region: the CPU baseline and its byte-for-byte spot check, GPU verification of sampled
+      inclusion proofs, and (N = 1) the secondary legs -- other policies, aggregation factors, the API layout, host buffers.
       N > 1: one rank per GPU.  Under a launcher (torch.distributed.run sets WORLD_SIZE) this process IS a rank; without one
       the process -- which has not touched the GPU -- starts `python -m torch.distributed.run --nproc-per-node N ... bench.py`
       as a child, relays rank 0's JSON line and exits with the child's code.
@@ -23,18 +26,18 @@ exchange is an all-gather of the N subtree-root records and an all-reduce of the
 
 Steps and wall budget.  Exactly --steps steps are timed, and `ms_per_step` is the wall time of one of them.  One step of
 configs[2] takes ~19 s, so a caller sizes --steps by `ms_per_step`.  The rest of the run has a wall budget (--budget-s,
-default 570 s counted from process start, including imports / build / context creation and a reserve for the legs after the
-timed region): warm-up steps beyond the first two are dropped when they do not fit, and the secondary legs are skipped when
-the budget is spent.  The line reports the steps actually run (`steps`, `warmup`) and what was asked for (`steps_requested`,
-`warmup_requested`).  A heartbeat goes to stderr after every step.
+default 570 s counted from process start, including imports / build / context creation and, with --full, a reserve for the
+legs after the timed region): warm-up steps beyond the first two are dropped when they do not fit, and the secondary legs are
+skipped when the budget is spent.  The line reports the steps actually run (`steps`, `warmup`) and what was asked for
+(`steps_requested`, `warmup_requested`).  A heartbeat goes to stderr after every step.
 
 --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, 64 MB at most): see
 dump_outputs().  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).  Everything in `roofline` outside
-`from_profiles` is measured by THIS run (HIP events on the launch streams inside the library).  The CPU oracle
-(oracle/) is used only for the `cpu_baseline` leg and a byte-for-byte spot check of sampled proofs -- never in the
-timed region.
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field); --full prints it as soon as the timed region
+ends and again, complete, after its legs.  Everything in `roofline` outside `from_profiles` is measured by THIS run (HIP
+events on the launch streams inside the library).  The CPU oracle (oracle/) is used only by --full's `cpu_baseline` leg and
+byte-for-byte spot check of sampled proofs -- never in the timed region.
 """
 import time
 
@@ -554,10 +557,12 @@ def mode_prove(args):
     # ---- warm-up: one step always; a second one (when asked for) is the warm step the timed loop is sized from -- the first one is
     # cold (allocations, code objects: ~3 s more) and would under-count what fits; further ones only if they fit
     deadline = T_PROC0 + args.budget_s
-    # what follows the timed region, as measured on the driver's run of round 3 (BENCH_r03: 34 s in all): CPU baseline 10 s + parity /
-    # verification legs ~9 s + the N = 1 secondary legs ~15 s + ~22 s for the full-size host-buffer leg (which falls back to a 2^16 sample
-    # when the budget is short); 15 % on top
-    post_reserve = 1.15 * ((args.cpu_budget_s + 4.0 if not args.no_cpu_baseline else 0.0) + 9.0 + (43.0 if (world == 1 and not args.no_secondary) else 0.0))
+    # what --full runs after the timed region, as measured in round 3 (BENCH_r03: 34 s in all): CPU baseline 10 s + parity /
+    # verification legs ~9 s + the N = 1 secondary legs ~15 s + ~22 s for the full-size host-buffer leg (which falls back to a 2^16
+    # sample when the budget is short); 15 % on top.  A plain run has no such legs.
+    post_reserve = 0.0
+    if args.full:
+        post_reserve = 1.15 * ((args.cpu_budget_s + 4.0 if not args.no_cpu_baseline else 0.0) + 9.0 + (43.0 if (world == 1 and not args.no_secondary) else 0.0))
     warm_req, steps_req = args.warmup, args.steps
     warm_done = 0
     t_step = None
@@ -687,7 +692,13 @@ def mode_prove(args):
     if preflight is not None and isinstance(multi_gpu, dict):
         multi_gpu["preflight"] = preflight
 
-    dumped = None                                  # --dump-outputs: what dump_outputs() wrote (set after the headline line)
+    dumped = None                                  # --dump-outputs: what dump_outputs() wrote (set after the timed region)
+
+    def dump():
+        out = dump_outputs(args.dump_outputs, prover, stats.checksum, int(stats.proof_bytes // max(1, stats.proofs)))
+        log("outputs of the last timed step: %d files, %.1f MB, %d of %d entities, in %s" %
+            (len(out["files"]), out["bytes"] / 1e6, out["entities"], out["entities_of_rank"], out["dir"]))
+        return out
 
     def make_line(cpu, parity, secondary, complete):
         return {
@@ -711,19 +722,26 @@ def mode_prove(args):
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "secondary": secondary,
             "checksum": "%016x" % stats.checksum,
             "outputs_dumped": dumped,
+            "full": bool(args.full),
             "complete": complete,
             "wall_s_since_process_start": time.time() - T_PROC0,
         }
 
-    # The headline goes out NOW, as soon as the timed region has ended: the legs below (CPU baseline, parity, secondary: ~60 s) come
-    # after it, and a run killed at the driver's limit must not lose the line.  The same line is printed again at the end with
+    if not args.full:
+        # a plain run ends here: the outputs when asked for, then the one line ("complete": it is all this run measures)
+        if args.dump_outputs:
+            dumped = dump()
+        print(json.dumps(make_line(None, None, None, True)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    # --full: the headline goes out NOW, as soon as the timed region has ended: the legs below (CPU baseline, parity, secondary: ~60 s)
+    # come after it, and a run killed at its time limit must not lose the line.  The same line is printed again at the end with
     # `cpu_baseline`, `parity` and `secondary` filled in ("complete": true); whoever reads the output takes the LAST line.
     print(json.dumps(make_line(None, None, None, False)), flush=True)
     if args.dump_outputs:
-        # before the secondary legs run the workload again: the arrays are those of the last timed step
-        dumped = dump_outputs(args.dump_outputs, prover, stats.checksum, int(stats.proof_bytes // max(1, stats.proofs)))
-        log("outputs of the last timed step: %d files, %.1f MB, %d of %d entities, in %s" %
-            (len(dumped["files"]), dumped["bytes"] / 1e6, dumped["entities"], dumped["entities_of_rank"], dumped["dir"]))
+        dumped = dump()                            # before the secondary legs run the workload again: the last timed step's arrays
     cpu = None
     parity = None
     if not args.no_cpu_baseline and os.path.exists(ORACLE_LIB) and prover.w is not None:
@@ -1480,16 +1498,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mode", choices=("prove", "build", "verify", "criterion"), default="prove")
     ap.add_argument("--budget-s", type=float, default=570.0,
-                    help="wall budget of the whole process, counted from its start: extra warm-up steps and the secondary legs run only if they fit "
-                         "(the timed steps are always --steps)")
-    ap.add_argument("--cpu-budget-s", type=float, default=10.0, help="wall budget of the CPU-baseline leg")
+                    help="wall budget of the whole process, counted from its start: extra warm-up steps and --full's secondary legs run only if "
+                         "they fit (the timed steps are always --steps)")
+    ap.add_argument("--cpu-budget-s", type=float, default=10.0, help="wall budget of --full's CPU-baseline leg")
     ap.add_argument("--no-pinned-leg", action="store_true", help="--mode verify: skip the extra passes from page-locked host buffers (profiling: keeps the kernel counts per pass)")
     ap.add_argument("--no-bad-proof-leg", action="store_true", help="--mode verify: skip the untimed pass with one bad proof (profiling: its per-proof re-check is not part of a pass)")
     ap.add_argument("--log2-entities", type=int, default=20,
                     help="entities IN TOTAL = 2^this (default 20: BASELINE configs[2], the metric's workload at every N); per GPU with --weak")
     ap.add_argument("--log2-entities-total", type=int, default=None, help="the same, spelled out (configs[3]: 22 with --gpus 8)")
     ap.add_argument("--weak", action="store_true", help="N > 1: weak scaling, 2^--log2-entities per GPU (default: strong, the total is divided)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (splitting policy, API layout, host buffers)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the CPU baseline + byte-for-byte spot check, GPU verification of sampled inclusion "
+                         "proofs and (N = 1) the secondary legs; a plain run does only what the headline line needs")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary legs (splitting policy, API layout, host buffers)")
     ap.add_argument("--no-inline-preflight", action="store_true", help="N > 1: skip the collective checks that run before the first step")
     ap.add_argument("--allow-exchange-fallback", action="store_true",
                     help="N > 1 over RCCL: time the run even if the library's communicator did not come up (torch.distributed carries the exchange)")
@@ -1513,6 +1534,8 @@ def main():
         if args.mode != "prove" or args.preflight:
             raise SystemExit("--dump-outputs applies to the proving workload (--mode prove, no --preflight)")
         args.dump_outputs = os.path.abspath(args.dump_outputs)
+    if args.full and (args.mode != "prove" or args.preflight):
+        raise SystemExit("--full applies to the proving workload (--mode prove, no --preflight): the other modes always run whole")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus < 1:

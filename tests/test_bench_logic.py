@@ -109,3 +109,18 @@ def test_dump_outputs_sample_and_format(tmp_path):
     assert len(np.unique(pos)) == s and np.all(np.diff(pos) > 0)
     for name in big[0]["files"]:
         assert np.array_equal(load(big[0]["dir"], name), load(big[1]["dir"], name)), name
+
+
+def test_full_is_off_by_default_and_only_for_the_proving_workload(monkeypatch):
+    """A plain run is the lean one; --full reaches mode_prove, and the modes that always run whole refuse it."""
+    seen = []
+    monkeypatch.setattr(bench, "mode_prove", lambda a: seen.append(a.full))
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    for argv, want in ((["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"], False), (["bench.py", "--full"], True)):
+        monkeypatch.setattr(sys, "argv", argv)
+        bench.main()
+        assert seen.pop() is want
+    for extra in (["--mode", "build"], ["--mode", "verify"], ["--mode", "criterion"], ["--preflight"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--full"] + extra)
+        with pytest.raises(SystemExit, match="--full"):
+            bench.main()

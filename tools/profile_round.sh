@@ -2,7 +2,7 @@
 export DAPOL_ENV_KNOBS=1     # the DAPOL_* knobs below are read only by a process that opts in
 # One GPU call that refreshes the evidence under profiles/: tools/profile_round.sh <tag>   (run from the repo root on the GPU box)
 #   gpurun_out/<tag>_ubench_madd.txt      VALU-only cost of the point operations (the MSM's issue roof)
-#   gpurun_out/<tag>_bench.json           python bench.py (default workload, with the CPU baseline)
+#   $OUT/<tag>_bench.json                 python bench.py --full (default workload, with the CPU baseline)
 #   gpurun_out/<tag>_stats/               rocprofv3 --kernel-trace --stats of the same command without the CPU leg
 #   gpurun_out/<tag>_pmc_*/               separate --pmc passes on 2^18 entities (two full chunks of 131,072 proofs)
 set -o pipefail
@@ -12,7 +12,7 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 [ -x build/ubench_madd ] && build/ubench_madd > $OUT/${tag}_ubench_madd.txt 2>&1
-python3 bench.py --steps 3 > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err || { tail -5 $OUT/${tag}_bench.err; exit 1; }
+python3 bench.py --steps 3 --full > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err || { tail -5 $OUT/${tag}_bench.err; exit 1; }
 tail -c 600 $OUT/${tag}_bench.json; echo
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${tag}_stats -o stats -- python3 $R/bench.py --no-cpu-baseline --no-secondary --steps 2 --warmup 1 > $OUT/${tag}_stats.log 2>&1 || { tail -5 $OUT/${tag}_stats.log; exit 1; }
