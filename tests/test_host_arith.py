@@ -4,6 +4,8 @@ import ctypes
 import hashlib
 import random
 
+import edge_scalars as E
+
 
 def buf(n):
     return ctypes.create_string_buffer(n)
@@ -116,6 +118,32 @@ def test_scalar_field(host_shim, pyref):
             dc = (ctypes.c_int * nwc)()
             host_shim.t_sc_recode_w(w, nwc, xc.to_bytes(32, "little"), dc)
             assert sum(int(dc[i]) << (w * i) for i in range(nwc)) == xc and all(-32768 <= int(v) <= 32767 for v in dc)
+        for w in range(17, 21):                                    # the widths whose digits need dig_t = int32 (17 is the bench profile's)
+            for nw, xx in ((255 // w + 1, x), (253 // w + 1, x % L)):
+                dw = (ctypes.c_int * nw)()
+                host_shim.t_sc_recode_w(w, nw, xx.to_bytes(32, "little"), dw)
+                assert [int(v) for v in dw] == E.recode(xx, w, nw)
+                assert sum(int(dw[i]) << (w * i) for i in range(nw)) == xx and all(abs(int(v)) <= (1 << (w - 1)) for v in dw)
+    # the crafted edge scalars (tests/edge_scalars.py) at every width the header allows, under both window-count conventions: the
+    # digits are exactly the big-integer recoder's -- row-end digits -2^(W-1), full carry chains, carry-only top windows, +2^(W-1) on top
+    hit_neg = hit_pos = 0
+    for w in range(8, 21):
+        half = 1 << (w - 1)
+        for kind in ("blinding", "canonical"):
+            nw = E.nwin_of(kind, w)
+            fams = dict(E.families(w, kind))
+            if kind == "blinding":                                 # a canonical scalar is also a legal input of the wider convention
+                fams.update({"c-" + k: v for k, v in E.families(w, "canonical").items()})
+                fams.update({"v-" + k: v for k, v in E.families(w, "value").items()})
+            for name, xx in fams.items():
+                dw = (ctypes.c_int * nw)()
+                host_shim.t_sc_recode_w(w, nw, xx.to_bytes(32, "little"), dw)
+                got = [int(v) for v in dw]
+                assert got == E.recode(xx, w, nw), (w, kind, name)
+                assert sum(d << (w * i) for i, d in enumerate(got)) == xx and all(abs(d) <= half for d in got), (w, kind, name)
+                hit_neg += got.count(-half)
+                hit_pos += got[-1] == half
+    assert hit_neg > 13 * 2 * 10 and hit_pos == 3                  # +half on top: 2^255 - 1 at W = 8 and 16, 2^255 - 2^247 at W = 8
 
 
 def test_hashes_and_transcript(host_shim, pyref):
