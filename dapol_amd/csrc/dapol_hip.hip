@@ -106,24 +106,12 @@ struct dapol_ctx {
     int max_parties = 0;
     int n_cu = 256;                                      // hipDeviceProp_t::multiProcessorCount (MI355X: 256)
     int msm_waves_per_cu = 4 * DAPOL_MSM_OCC;            // resident wavefronts of k_rp_msm per CU (occupancy API, dapol_ctx_create)
-    unsigned msm_dyn_lds = 0;                            // dynamic LDS bytes of the MSM launches: caps the residency (DAPOL_MSM_OCC_CAP)
     // wavefronts the dominant kernel keeps resident on the chip: launches are sized in whole rounds of this many
     size_t resident_waves() const { return (size_t)n_cu * (size_t)msm_waves_per_cu; }
     hipStream_t stream = nullptr;
     hipStream_t side[3] = {nullptr, nullptr, nullptr};   // further pipelines of the range prover (several chunks in flight)
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_v[4] = {nullptr, nullptr, nullptr, nullptr};   // the verifier's commitments landing in column blocks (host_verify.inc: VArrival)
-    // Opt-in experiment (DAPOL_MSM_SERIAL=1, measured slower): the generator-stationary MSMs of ALL chunks in flight through ONE
-    // stream, one sweep at a time, the other chunks' scalar kernels beside it.  ev_msm_pre / _post[chunk lane] order a chunk's own
-    // stream around its MSMs.
-    hipStream_t msm_stream = nullptr;
-    hipEvent_t ev_msm_pre[4] = {nullptr, nullptr, nullptr, nullptr}, ev_msm_post[4] = {nullptr, nullptr, nullptr, nullptr};
-    // Measurement knob DAPOL_STREAM_LAYOUT (round 4, profiles/r07*_stream_layout*.txt): streams with CU masks / priorities, made on
-    // first use.  layout_lane[] carry the chunks, layout_msm the VALU-bound launches of all of them when the layout separates those.
-    std::string layout_name;
-    hipStream_t layout_lane[2] = {nullptr, nullptr}, layout_msm = nullptr;
-    hipEvent_t layout_ev[2] = {nullptr, nullptr};
-    bool layout_split_msm = false;
     DevBuf<int32_t> table;       // window tables
     DevBuf<uint32_t> gens_comp;  // compressed base points of every row (for dapol_ctx_generator)
     TableView tv{};
@@ -189,53 +177,6 @@ static bool options_ok(const dapol_options* o) {
     if (o->profile != DAPOL_PROFILE_BENCH && o->profile != DAPOL_PROFILE_HOST) return false;
     return true;
 }
-// DAPOL_STREAM_LAYOUT=<name> (measurement knob): where the chunks in flight and their VALU-bound launches run.
-//   split_xcd     two chunks in flight, each on its own four XCDs (128 CUs, four L2s)
-//   split_cu      two chunks in flight, each on 16 CUs of every XCD
-//   msm:<K>       the VALU-bound launches of all chunks (sweeps, materialisation, tail MSM and tables) one after the other on 256 - K
-//                 CUs, everything else (streaming scalar kernels, Fiat-Shamir) on the other K CUs (K / 8 per XCD)
-//   prio          no masks: the VALU-bound launches on a LOW-priority stream, one after the other, the rest on HIGH-priority streams
-//   prio_lanes    no masks, no separation: two chunks in flight on two streams as by default, but created with HIGH priority for
-//                 the second (so that one chunk's launches overtake the other's instead of sharing)
-// A CU-mask bit i stands for CU i / 8 of XCD i % 8 (the driver deals the mask out round-robin over the XCCs).
-static int32_t ensure_stream_layout(dapol_ctx* c, const char* name) {
-    if (c->layout_name == name) return DAPOL_OK;
-    for (int i = 0; i < 2; i++) if (c->layout_lane[i]) { (void)hipStreamDestroy(c->layout_lane[i]); c->layout_lane[i] = nullptr; }
-    if (c->layout_msm) { (void)hipStreamDestroy(c->layout_msm); c->layout_msm = nullptr; }
-    c->layout_name.clear();
-    c->layout_split_msm = false;
-    for (int i = 0; i < 2; i++) if (!c->layout_ev[i]) HIPCHK(hipEventCreateWithFlags(&c->layout_ev[i], hipEventDisableTiming));
-    const int ncu = c->n_cu, words = (ncu + 31) / 32;
-    auto mask_of = [&](auto pred) { std::vector<uint32_t> m((size_t)words, 0u); for (int i = 0; i < ncu; i++) if (pred(i)) m[i >> 5] |= 1u << (i & 31); return m; };
-    const std::string n(name);
-    if (n == "split_xcd" || n == "split_cu") {
-        for (int h = 0; h < 2; h++) {
-            auto m = n == "split_xcd" ? mask_of([&](int i) { return ((i % 8) < 4) == (h == 0); }) : mask_of([&](int i) { return (i < ncu / 2) == (h == 0); });
-            HIPCHK(hipExtStreamCreateWithCUMask(&c->layout_lane[h], (uint32_t)words, m.data()));
-        }
-    } else if (n.rfind("msm:", 0) == 0) {
-        const int K = atoi(n.c_str() + 4);
-        if (K < 8 || K > ncu / 2 || K % 8) return fail(DAPOL_ERR_INVALID_ARGUMENT, "DAPOL_STREAM_LAYOUT=msm:<K>: K must be a multiple of 8 in [8, CUs / 2]");
-        auto small = mask_of([&](int i) { return i < K; }), big = mask_of([&](int i) { return i >= K; });
-        for (int h = 0; h < 2; h++) HIPCHK(hipExtStreamCreateWithCUMask(&c->layout_lane[h], (uint32_t)words, small.data()));
-        HIPCHK(hipExtStreamCreateWithCUMask(&c->layout_msm, (uint32_t)words, big.data()));
-        c->layout_split_msm = true;
-    } else if (n == "prio" || n == "prio_lanes") {
-        int lo = 0, hi = 0;                                   // (numerically lower = higher priority)
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        if (n == "prio") {
-            for (int h = 0; h < 2; h++) HIPCHK(hipStreamCreateWithPriority(&c->layout_lane[h], hipStreamDefault, hi));
-            HIPCHK(hipStreamCreateWithPriority(&c->layout_msm, hipStreamDefault, lo));
-            c->layout_split_msm = true;
-        } else {
-            HIPCHK(hipStreamCreateWithPriority(&c->layout_lane[0], hipStreamDefault, lo));
-            HIPCHK(hipStreamCreateWithPriority(&c->layout_lane[1], hipStreamDefault, hi));
-        }
-    } else return fail(DAPOL_ERR_INVALID_ARGUMENT, "unknown DAPOL_STREAM_LAYOUT");
-    c->layout_name = n;
-    return DAPOL_OK;
-}
-
 // A FORK hands kernels that read and write the context's scratch (or a call's own buffers) to a side stream; the matching JOIN makes
 // the context's stream wait for them.  An early return between the two -- any HIPCHK / LAUNCH_CHECK -- would leave those kernels
 // running while the caller's next call reuses the scratch, or after the call's buffers are freed.  This guard, one per forking
@@ -249,12 +190,7 @@ static int32_t ctx_make_streams(dapol_ctx* c) {
         HIPCHK(hipStreamCreate(&c->side[i]));
         HIPCHK(hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
     }
-    HIPCHK(hipStreamCreate(&c->msm_stream));
     for (int i = 0; i < 4; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_v[i], hipEventDisableTiming));
-    for (int i = 0; i < 4; i++) {
-        HIPCHK(hipEventCreateWithFlags(&c->ev_msm_pre[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_msm_post[i], hipEventDisableTiming));
-    }
     return DAPOL_OK;
 }
 static void ctx_free_streams(dapol_ctx* ctx) {
@@ -266,16 +202,6 @@ static void ctx_free_streams(dapol_ctx* ctx) {
     }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     for (int i = 0; i < 4; i++) if (ctx->ev_v[i]) (void)hipEventDestroy(ctx->ev_v[i]);
-    if (ctx->msm_stream) (void)hipStreamDestroy(ctx->msm_stream);
-    for (int i = 0; i < 2; i++) {
-        if (ctx->layout_lane[i]) (void)hipStreamDestroy(ctx->layout_lane[i]);
-        if (ctx->layout_ev[i]) (void)hipEventDestroy(ctx->layout_ev[i]);
-    }
-    if (ctx->layout_msm) (void)hipStreamDestroy(ctx->layout_msm);
-    for (int i = 0; i < 4; i++) {
-        if (ctx->ev_msm_pre[i]) (void)hipEventDestroy(ctx->ev_msm_pre[i]);
-        if (ctx->ev_msm_post[i]) (void)hipEventDestroy(ctx->ev_msm_post[i]);
-    }
 }
 // Lane i (0 = the context itself) for one group of a small call's sub-proofs: see dapol_ctx::aux.
 static int32_t ctx_lane(dapol_ctx* ctx, int i, dapol_ctx** out) {
@@ -284,7 +210,7 @@ static int32_t ctx_lane(dapol_ctx* ctx, int i, dapol_ctx** out) {
     if (!a) {
         dapol_ctx* n = new dapol_ctx();
         n->opt = ctx->opt; n->device = ctx->device; n->max_parties = ctx->max_parties; n->n_cu = ctx->n_cu;
-        n->msm_waves_per_cu = ctx->msm_waves_per_cu; n->msm_dyn_lds = ctx->msm_dyn_lds;
+        n->msm_waves_per_cu = ctx->msm_waves_per_cu;
         n->tv = ctx->tv;                                  // the same tables: only the primary owns (and frees) them
         int32_t rc = ctx_make_streams(n);
         if (rc) { ctx_free_streams(n); delete n; return rc; }
@@ -298,19 +224,14 @@ static int32_t ctx_lane(dapol_ctx* ctx, int i, dapol_ctx** out) {
 struct ForkGuard {
     dapol_ctx* c;
     bool open[3] = {false, false, false};
-    hipStream_t extra = nullptr;     // one more stream that carries this call's kernels while the guard is armed (the measurement knobs'
-    bool extra_open = false;         // MSM stream: DAPOL_MSM_SERIAL / stream layouts); closed by done() on the normal path
     explicit ForkGuard(dapol_ctx* c_) : c(c_) {}
     ForkGuard(const ForkGuard&) = delete;
     ForkGuard& operator=(const ForkGuard&) = delete;
     void forked(int i) { open[i] = true; }
     void joined(int i) { open[i] = false; }
-    void also(hipStream_t s) { extra = s; extra_open = s != nullptr; }
-    void done() { extra_open = false; }
     ~ForkGuard() {
         for (int i = 0; i < 3; i++)
             if (open[i]) { (void)hipStreamSynchronize(c->side[i]); g_fork_guard_waits.fetch_add(1, std::memory_order_relaxed); }
-        if (extra_open) { (void)hipStreamSynchronize(extra); g_fork_guard_waits.fetch_add(1, std::memory_order_relaxed); }
     }
 };
 // Test knob (behind BOTH opt-ins, test_knob above): DAPOL_TEST_FAIL_AFTER_FORK=<site> makes the named site return an error right
@@ -385,18 +306,9 @@ int32_t dapol_ctx_create_opts(int32_t device, int32_t max_parties, int32_t diges
         HIPCHK(hipGetDeviceProperties(&prop, device));
         if (prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
         // Residency of the dominant kernel (one wavefront per block): what its registers and LDS allow -- asked of the runtime,
-        // not assumed.  DAPOL_MSM_OCC_CAP=<waves per SIMD> lowers it by padding the launch's LDS (A/B knob: at the socket power
-        // cap more resident wavefronts are not automatically faster, profiles/r01_madchain_ab.txt).
-        if (const char* e = knob("DAPOL_MSM_OCC_CAP")) {
-            int cap = atoi(e);
-            const size_t lds_cu = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : 163840, stat = 0;   // (the kernel itself uses no LDS)
-            if (cap >= 1 && cap <= 8) {
-                size_t per_block = lds_cu / (size_t)(4 * cap) / 512 * 512;          // LDS is granted in 512-byte granules
-                if (per_block > stat) c->msm_dyn_lds = (unsigned)(per_block - stat);
-            }
-        }
+        // not assumed.
         int blocks = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_rp_msm<MSM_PLAIN, 4>, 64, c->msm_dyn_lds) == hipSuccess && blocks > 0)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_rp_msm<MSM_PLAIN, 4>, 64, 0) == hipSuccess && blocks > 0)
             c->msm_waves_per_cu = blocks;
         else (void)hipGetLastError();
     }

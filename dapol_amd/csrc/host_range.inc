@@ -3,6 +3,7 @@
 
 #include <cstdlib>
 #include "policy_plan.inc"
+#include "prove_plan.inc"
 
 struct MsmTiming {                       // HIP-event timing of the fixed-base MSM kernels, on the stream they run on
     // Brackets come in two kinds: 0 = the plain MSMs (S commitment, never-fold rounds: k_rp_msm_gs / k_rp_msm<0, .>),
@@ -69,25 +70,14 @@ struct MsmTiming {                       // HIP-event timing of the fixed-base M
         else if ((fs) == 1) hipLaunchKernelGGL(kernel<1>, dim3(nblk(2 * (cb), 64)), dim3(64), 0, st, __VA_ARGS__);   \
         else hipLaunchKernelGGL(kernel<0>, dim3(nblk((cb), 64)), dim3(64), 0, st, __VA_ARGS__);                      \
     } while (0)
-enum { FS_PARTS_MAX = 8 };        // most wavefronts per proof of k_rp_poly / k_rp_lr in small calls
-// Small calls: into how many wavefronts a proof's main MSM may be split (DAPOL_SMALL_SPLIT overrides; a power of two <= 64).
-static int small_split_cap(bool use_hi) {
-    if (const char* e = knob("DAPOL_SMALL_SPLIT")) { int v = atoi(e); if (v >= 1 && v <= 64 && !(v & (v - 1))) return v; }
-    return use_hi ? 64 : 8;
-}
-// Most wavefronts a launch of the four-lanes-per-point kernels may have (DAPOL_QUAD_MAX_WAVES overrides the measured defaults).
-static size_t quad_max_waves(size_t dflt) {
-    if (const char* e = knob("DAPOL_QUAD_MAX_WAVES")) { long long v = atoll(e); if (v > 0) return (size_t)v; }
-    return dflt;
-}
 // The fixed-base MSM with LPL lanes per list (32 / LPL proofs per wavefront).
-static void launch_msm(hipStream_t st, const RangeArgs& A, const TableView& tv, int round, int lpl, unsigned dyn_lds = 0) {
+static void launch_msm(hipStream_t st, const RangeArgs& A, const TableView& tv, int round, int lpl) {
     const unsigned B = (unsigned)A.B, S = (unsigned)(A.nsplit > 1 ? A.nsplit : 1);
-    if (lpl == 8) hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 8>), dim3((B + 3) / 4 * S), dim3(64), dyn_lds, st, A, tv, round);
-    else if (lpl == 4) hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 4>), dim3((B + 7) / 8 * S), dim3(64), dyn_lds, st, A, tv, round);
-    else if (lpl == 2) hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 2>), dim3((B + 15) / 16 * S), dim3(64), dyn_lds, st, A, tv, round);
-    else if (lpl == 16) hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 16>), dim3((B + 1) / 2 * S), dim3(64), dyn_lds, st, A, tv, round);
-    else hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 32>), dim3(B * S), dim3(64), dyn_lds, st, A, tv, round);
+    if (lpl == 8) hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 8>), dim3((B + 3) / 4 * S), dim3(64), 0, st, A, tv, round);
+    else if (lpl == 4) hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 4>), dim3((B + 7) / 8 * S), dim3(64), 0, st, A, tv, round);
+    else if (lpl == 2) hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 2>), dim3((B + 15) / 16 * S), dim3(64), 0, st, A, tv, round);
+    else if (lpl == 16) hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 16>), dim3((B + 1) / 2 * S), dim3(64), 0, st, A, tv, round);
+    else hipLaunchKernelGGL((k_rp_msm<MSM_PLAIN, 32>), dim3(B * S), dim3(64), 0, st, A, tv, round);
 }
 // The tail argument's MSM over the per-proof tables: 32 terms per list, LPL lanes per list.
 static void launch_msm_tail(hipStream_t st, const RangeArgs& At, const TableView& tvt, int round, int lpl) {
@@ -97,49 +87,6 @@ static void launch_msm_tail(hipStream_t st, const RangeArgs& At, const TableView
     else if (lpl == 32) hipLaunchKernelGGL((k_rp_msm<MSM_TAIL, 32>), dim3(B), dim3(64), 0, st, At, tvt, round);
     else if (lpl == 8) hipLaunchKernelGGL((k_rp_msm<MSM_TAIL, 8>), dim3((B + 3) / 4), dim3(64), 0, st, At, tvt, round);
     else hipLaunchKernelGGL((k_rp_msm<MSM_TAIL, 4>), dim3((B + 7) / 8), dim3(64), 0, st, At, tvt, round);
-}
-// Lanes per term list for launches of `proofs` proofs: the candidate that minimises (rounds of resident wavefronts: CUs x 4 x 3) x
-// (mixed adds + shared doublings per lane).  Few lanes per list amortise the doublings; many fill the chip when the call is small.
-// shared_simd (the tail MSM's picker since the end of round 3): what was measured instead of that -- k wavefronts sharing a SIMD take
-// about 1 + 0.23 (k - 1) times a lone wavefront's chain (a lone one leaves the issue slots between its dependent multiply-adds
-// and under its table lookups empty: 16,384 proofs 2 -> 8 lanes per list = 1 -> 4 wavefronts per SIMD with a third of the chain each,
-// 330.9 -> 316.7 ms per call), and one proof per wavefront pays double per addition (64 different rows per lookup instruction):
-// profiles/r05w_tail_lpl_sweep.txt.
-static int pick_lanes_per_list(size_t proofs, int terms_per_list, int nwin, int wbits, const int* cand, int ncand, size_t resident, size_t n_simd,
-                               bool shared_simd = false) {
-    // A SIMD interleaves its resident wavefronts, so a round in which it holds k of them takes about k times a lone wavefront's
-    // chain: cost = (chain per lane) x (wavefronts per SIMD, summed over the rounds).  (Round 1 counted rounds only, which made
-    // one proof per wavefront look free for a few thousand proofs: 190 ms instead of 114 for 4,096, profiles/r02_midsize_ab.txt.)
-    int best = cand[0];
-    double best_cost = 1e300;
-    const size_t occ = n_simd ? (resident + n_simd - 1) / n_simd : 1;
-    for (int i = 0; i < ncand; i++) {
-        int lpl = cand[i];
-        size_t waves = (proofs + (size_t)(32 / lpl) - 1) / (size_t)(32 / lpl);
-        const size_t full = waves / resident, rem = waves % resident;
-        const size_t krem = rem ? (rem + n_simd - 1) / (n_simd ? n_simd : 1) : 0;
-        double per_simd = (double)(full * occ) + (double)krem;
-        if (shared_simd) per_simd = (double)full * (1.0 + 0.23 * (double)(occ - 1)) + (krem ? 1.0 + 0.23 * (double)(krem - 1) : 0.0);
-        double per_lane = (double)((terms_per_list + lpl - 1) / lpl) * nwin * (shared_simd && lpl == 32 ? 2.0 : 1.0) + (double)nwin * wbits;
-        double cost = per_simd * per_lane;
-        if (cost < best_cost) { best_cost = cost; best = lpl; }
-    }
-    return best;
-}
-static int tail_lanes_per_list(bool small_call = false) {
-    const char* e = knob("DAPOL_TAIL_LPL");
-    if (e) { int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 32) return v; }
-    if (small_call) return 32;     // one proof per wavefront: latency, not throughput
-    return 2;                 // measured 2^16 proofs, m = 32: 36.1K / 37.0K / 35.9K entities/s at 4 / 2 / 8 (profiles/r01_tail_ab.txt)
-}
-// big_batch: the call carries at least one full chunk (whole rounds of resident wavefronts), so 16 proofs per wavefront
-// (LPL = 2: 1,024 terms per lane, the 255 shared doublings amortised over 15,360 additions) still fill the chip; smaller calls
-// keep 4 per wavefront (finer granularity).  Measured interleaved (profiles/r02_lpl2_tail6_ab.txt): LPL 4 -> 2 +0.9 % at
-// 2^18 proofs, +1.5 % at 2^20.
-static int msm_lanes_per_list(int N, bool big_batch = false) {
-    const char* e = knob("DAPOL_LPL");
-    if (e) { int v = atoi(e); if (v == 2 || v == 4 || v == 8 || v == 16 || v == 32) return v; }
-    return N >= 1024 ? (big_batch ? 2 : 8) : (N >= 256 ? 16 : 32);
 }
 
 // Scratch budget of the range prover / verifier: DAPOL_SCRATCH_GB if set; else 130 GB (two 73,728-proof chunks of the
@@ -194,284 +141,238 @@ struct PendingProve {
     }
     ~PendingProve() { if (armed) (void)hipStreamSynchronize(ctx->stream); }
 };
+
+// One chunk in flight owns one share of the context's scratch: the buffers of RangeArgs (A: everything else is the call's), the
+// partial points of a split main MSM (two lists) and of a split materialisation, and the sweep's accumulators.
+struct ProveLane {
+    RangeArgs A;
+    int32_t* split[3];
+    int32_t* gsacc;
+};
+static ProveLane carve_lane(const ProvePlan& P, RangeArgs A, uint8_t* base) {
+    ProveLane L{};
+    const size_t chunk = P.chunk, N = (size_t)P.N, T = (size_t)P.tail_n;
+    size_t o = 0;
+    A.a = (sc*)(base + o); o += chunk * N * sizeof(sc);
+    A.b = (sc*)(base + o); o += chunk * N * sizeof(sc);
+    A.s1 = (sc*)(base + o); o += chunk * N * sizeof(sc);
+    A.s2 = (sc*)(base + o); o += chunk * N * sizeof(sc);
+    A.dig = (dig_t*)(base + o); o += align_up(chunk * P.dig_elems * sizeof(dig_t), 256);
+    A.st = (ProofState*)(base + o); o += align_up(chunk * sizeof(ProofState), 256);
+    A.PA = (int32_t*)(base + o); o += chunk * 160;
+    A.P0 = (int32_t*)(base + o); o += chunk * 160;
+    A.P1 = (int32_t*)(base + o); o += chunk * 160;
+    A.tailT = (int32_t*)(base + o); o += chunk * 2 * T * TAIL_ROW_WORDS * 4;
+    A.tail_a = (sc*)(base + o); o += chunk * T * sizeof(sc);
+    A.tail_b = (sc*)(base + o); o += chunk * T * sizeof(sc);
+    A.tail_s1 = (sc*)(base + o); o += chunk * T * sizeof(sc);
+    A.tail_s2 = (sc*)(base + o); o += chunk * T * sizeof(sc);
+    A.fs_part = (sc*)(base + o); o += chunk * FS_PARTS_MAX * 3 * sizeof(sc);
+    A.stab = P.stab_bytes ? (sc*)(base + o) : nullptr; o += chunk * P.stab_bytes;
+    L.gsacc = (int32_t*)(base + o); o += chunk * P.acc_bytes;
+    o = align_up(o, 256);
+    // (the split buffers stay LAST: split_bytes only counts them when a split is in use)
+    L.split[0] = (int32_t*)(base + o); o += chunk * (size_t)P.part_split() * 160;
+    L.split[1] = (int32_t*)(base + o); o += chunk * (size_t)P.part_split() * 160;
+    o = align_up(o, 256);
+    L.split[2] = (int32_t*)(base + o);
+    L.A = A;
+    return L;
+}
+
+// The fixed-base MSM of one round of the main argument for the chunk A (round -1: the S commitment), split or not.
+static void launch_main_msm(dapol_ctx* ctx, const ProvePlan& P, const ProveLane& L, const RangeArgs& A, hipStream_t st, int round, MsmTiming* tm) {
+    const size_t cb = A.B;
+    if (P.gs) {                                           // large calls: sweep the generators, a tile of rows per launch
+        const int LW = P.gs_LW;
+        const unsigned g_acc = nblk(cb * (size_t)LW, 64);
+        // calls of a few thousand proofs: slices of each list side by side (lanes enough to fill the chip)
+        const int ns = P.slices_for(cb), slice_rows = A.N / ns, tile = P.tile_for(cb, ns);
+        const size_t side_words = (size_t)4 * FE_NL * cb * LW * ns;         // the two lists' accumulators, one after the other
+        for (int side = 0; side < 2; side++)
+            for (int q0 = 0; q0 < slice_rows; q0 += tile) {
+                const int nq = slice_rows - q0 < tile ? slice_rows - q0 : tile;
+                if (LW < A.nwin)
+                    hipLaunchKernelGGL(k_rp_msm_gs_hi, dim3(g_acc, ns), dim3(64), 0, st, A, ctx->tv, round, side, q0, nq, q0 == 0 ? 1 : 0,
+                                       L.gsacc + side * side_words, slice_rows, LW);
+                else
+                    hipLaunchKernelGGL(k_rp_msm_gs, dim3(g_acc, ns), dim3(64), 0, st, A, ctx->tv, round, side, q0, nq, q0 == 0 ? 1 : 0,
+                                       L.gsacc + side * side_words, slice_rows);
+            }
+        if (ns > 1) hipLaunchKernelGGL(k_rp_gs_sum_slices, dim3(nblk(2 * cb * (size_t)LW, 64)), dim3(64), 0, st, A, L.gsacc, side_words, ns, LW);
+        hipLaunchKernelGGL(k_rp_gs_combine, dim3(nblk(2 * cb, 64)), dim3(64), 0, st, A, L.gsacc, side_words, ns, LW);
+        if (tm) tm->count(0, 2 * (size_t)((slice_rows + tile - 1) / tile));
+    } else if (P.part_split() > 1) {                      // small calls: a proof's term range over several wavefronts, partials summed
+        RangeArgs As = A;
+        As.nsplit = P.part_split(); As.P0 = L.split[0]; As.P1 = L.split[1];
+        // a few proofs: one point per four lanes (k_rp_msm_quad)
+        if (P.quad_split) hipLaunchKernelGGL(k_rp_msm_quad, dim3((unsigned)(cb * (size_t)P.quad_split)), dim3(64), 0, st, As, ctx->tv, round);
+        else launch_msm(st, As, ctx->tv, round, P.lpl);
+        hipLaunchKernelGGL(k_rp_sum_splits, dim3((unsigned)(2 * cb)), dim3(64), 0, st, cb, As.nsplit, As.P0, As.P1, A.P0, A.P1);
+    } else {
+        launch_msm(st, A, ctx->tv, round, P.lpl);
+        if (tm) tm->count(0, 1);
+    }
+}
+
+// Materialises the 2T folded generators of the chunk A into its per-proof tail tables' input (A.tailT).
+static int32_t launch_materialise(dapol_ctx* ctx, const ProvePlan& P, const ProveLane& L, const RangeArgs& A, hipStream_t st, MsmTiming* tm) {
+    const size_t cb = A.B, T = (size_t)P.tail_n;
+    const unsigned g_tail = (unsigned)(cb * (size_t)(P.tail_n / 32));
+    if (P.gs_mat) {                                       // a class (one folded generator of every proof) per tile, MAT_GROUP classes per Horner launch
+        const int LW = P.mat_LW(), cpl = P.mat_cpl(cb);
+        const unsigned g_cls = nblk(cb * (size_t)LW, 64);
+        const size_t slot_words = (size_t)4 * FE_NL * cb * LW;
+        for (int side = 0; side < 2; side++)
+            for (int c0 = 0; c0 < P.tail_n; c0 += MAT_GROUP) {
+                const int nc = P.tail_n - c0 < MAT_GROUP ? P.tail_n - c0 : MAT_GROUP;
+                for (int c = 0; c < nc; c += cpl) {               // cpl classes per launch (1 when one class's lanes fill the chip)
+                    const int ny = nc - c < cpl ? nc - c : cpl;
+                    hipLaunchKernelGGL(k_rp_mat_gs, dim3(g_cls, ny), dim3(64), 0, st, A, ctx->tv, side, c0 + c, 0, LW, L.gsacc + c * slot_words);
+                    if (LW < A.nwin) hipLaunchKernelGGL(k_rp_mat_gs, dim3(g_cls, ny), dim3(64), 0, st, A, ctx->tv, side, c0 + c, 1, LW, L.gsacc + c * slot_words);
+                }
+                hipLaunchKernelGGL(k_rp_mat_gs_horner, dim3(nblk(cb * (size_t)nc, 64)), dim3(64), 0, st, A, side, c0, nc, LW, L.gsacc);
+            }
+        if (tm) tm->count(1, 2 * (size_t)((P.tail_n + cpl - 1) / cpl) * (LW < A.nwin ? 2 : 1));
+    } else if (P.mat_split > 1) {
+        RangeArgs Am = A;
+        Am.nsplit = P.mat_split; Am.P0 = L.split[2];
+        hipLaunchKernelGGL((k_rp_msm<MSM_MATERIALIZE, 32>), dim3(g_tail * (unsigned)P.mat_split), dim3(64), 0, st, Am, ctx->tv, -1); LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_rp_sum_mat, dim3(nblk(cb * 2 * T, 64)), dim3(64), 0, st, cb * 2 * T, P.mat_split, Am.P0, A.tailT);
+    } else {
+        hipLaunchKernelGGL((k_rp_msm<MSM_MATERIALIZE, 32>), dim3(g_tail), dim3(64), 0, st, A, ctx->tv, -1);
+        if (tm) tm->count(1, 1);
+    }
+    LAUNCH_CHECK();
+    return DAPOL_OK;
+}
+
+// Queues every kernel of one chunk on the stream st.  A: the lane's buffers (L.A) with the chunk's inputs, outputs and B filled in.
+// Only a small call's A commitment leaves st (ProvePlan::side_A: forked to ctx->side[2] and joined again in here, under fg).
+static int32_t queue_chunk(dapol_ctx* ctx, const ProvePlan& P, const ProveLane& L, RangeArgs A, hipStream_t st, ForkGuard& fg, uint32_t* d_err,
+                           MsmTiming* tm) {
+    const size_t cb = A.B;
+    const int fs_shape = P.fs_shape, nf_rounds = P.nf_rounds();
+    sc* const stab_buf = A.stab;
+    if (!P.stab_main) A.stab = nullptr;
+    const unsigned g_wave = (unsigned)cb, g_lane = nblk(cb, 64), g_dig = (unsigned)(cb * (size_t)(A.TP / 64));
+    const unsigned g_gsdig = nblk(cb * (size_t)(2 * A.N), 64);               // generator-stationary producers: a thread per term
+    hipLaunchKernelGGL(k_rp_nonce_key, dim3(g_lane), dim3(64), 0, st, A); LAUNCH_CHECK();
+    if (P.gs) hipLaunchKernelGGL(k_rp_nonces_gs, dim3(g_gsdig), dim3(64), 0, st, A);
+    else hipLaunchKernelGGL(k_rp_nonces, dim3(g_dig), dim3(64), 0, st, A);
+    LAUNCH_CHECK();
+    if (P.side_A) {
+        HIPCHK(hipEventRecord(ctx->ev_fork, st));
+        HIPCHK(hipStreamWaitEvent(ctx->side[2], ctx->ev_fork, 0));
+        fg.forked(2);
+        hipLaunchKernelGGL(k_rp_A, dim3(g_wave), dim3(64), 0, ctx->side[2], A, ctx->tv); LAUNCH_CHECK();
+        HIPCHK(hipEventRecord(ctx->ev_join[2], ctx->side[2]));
+        FAULT_AFTER_FORK("prove_A");
+    } else if (P.a_lane(cb)) {
+        hipLaunchKernelGGL(k_rp_A_lane, dim3(g_lane), dim3(64), 0, st, A, ctx->tv); LAUNCH_CHECK();
+    } else {
+        hipLaunchKernelGGL(k_rp_A, dim3(g_wave), dim3(64), 0, st, A, ctx->tv); LAUNCH_CHECK();
+    }
+    if (tm) HIPCHK(tm->mark(st));
+    launch_main_msm(ctx, P, L, A, st, -1, tm); LAUNCH_CHECK();
+    if (tm) HIPCHK(tm->mark(st));
+    if (P.side_A) { HIPCHK(hipStreamWaitEvent(st, ctx->ev_join[2], 0)); fg.joined(2); }
+    LAUNCH_FS(k_rp_finish1, fs_shape, cb, st, A, ctx->tv); LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_rp_poly, dim3(g_wave * (unsigned)A.fs_parts), dim3(64), 0, st, A); LAUNCH_CHECK();
+    LAUNCH_FS(k_rp_finish2, fs_shape, cb, st, A, ctx->tv); LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_rp_lr, dim3(g_wave * (unsigned)A.fs_parts), dim3(64), 0, st, A); LAUNCH_CHECK();
+    if (fs_shape == 2) hipLaunchKernelGGL(k_rp_finish3<2>, dim3(g_wave), dim3(64), 0, st, A);
+    else hipLaunchKernelGGL(k_rp_finish3<0>, dim3(g_lane), dim3(64), 0, st, A);
+    LAUNCH_CHECK();
+    for (int k = 0; k < nf_rounds; k++) {
+        if (P.gs) hipLaunchKernelGGL(k_rp_round_prep_gs, dim3(g_gsdig), dim3(64), 0, st, A, k);
+        else hipLaunchKernelGGL(k_rp_round_prep, dim3(g_dig), dim3(64), 0, st, A, k);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_rp_round_ip, dim3(g_wave), dim3(64), 0, st, A, k); LAUNCH_CHECK();
+        if (tm) HIPCHK(tm->mark(st));
+        launch_main_msm(ctx, P, L, A, st, k, tm); LAUNCH_CHECK();
+        if (tm) HIPCHK(tm->mark(st));
+        LAUNCH_FS(k_rp_round_finish, fs_shape, cb, st, A, ctx->tv, k); LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_rp_fold, dim3(fold_blocks(A, cb, k)), dim3(256), 0, st, A, k);
+        LAUNCH_CHECK();
+    }
+    if (nf_rounds == A.lgN) {                             // no tail: the main argument went all the way
+        hipLaunchKernelGGL(k_rp_final, dim3(g_lane), dim3(64), 0, st, A, d_err); LAUNCH_CHECK();
+        return DAPOL_OK;
+    }
+    if (P.gs_mat) hipLaunchKernelGGL(k_rp_mat_prep_gs, dim3(g_gsdig), dim3(64), 0, st, A);
+    else hipLaunchKernelGGL(k_rp_mat_prep, dim3(g_dig), dim3(64), 0, st, A);
+    LAUNCH_CHECK();
+    if (tm) HIPCHK(tm->mark(st, 1));
+    { int32_t rc = launch_materialise(ctx, P, L, A, st, tm); if (rc) return rc; }
+    if (tm) HIPCHK(tm->mark(st, 1));
+    const unsigned g_tail = (unsigned)(cb * (size_t)(P.tail_n / 32));
+    {
+        RangeArgs Ai = A;
+        Ai.stab = P.stab_tail ? stab_buf : nullptr;           // (k_rp_tail_table also resets the tables for the tail argument)
+        hipLaunchKernelGGL(k_rp_tail_table, dim3(g_tail), dim3(64), 0, st, Ai); LAUNCH_CHECK();
+    }
+    // The remaining rounds: the same never-fold kernels on the length-T argument over the proof's own table.
+    RangeArgs At = A;
+    At.N = P.tail_n; At.lgN = P.tail_lgn; At.TP = 2 * P.tail_n; At.wbits = TAIL_WBITS; At.nwin = TAIL_NWIN; At.nsplit = 0;
+    At.a = A.tail_a; At.b = A.tail_b; At.s1 = A.tail_s1; At.s2 = A.tail_s2;
+    At.stab = P.stab_tail ? stab_buf : nullptr;
+    At.out_round0 = nf_rounds;
+    const TableView tvt{A.tailT, 1, TAIL_WBITS, 0, 0};
+    for (int k = 0; k < P.tail_lgn; k++) {
+        hipLaunchKernelGGL(k_rp_round_prep, dim3(g_tail), dim3(64), 0, st, At, k); LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_rp_round_ip, dim3(g_wave), dim3(64), 0, st, At, k); LAUNCH_CHECK();
+        launch_msm_tail(st, At, tvt, k, P.tail_lpl); LAUNCH_CHECK();
+        LAUNCH_FS(k_rp_round_finish, fs_shape, cb, st, At, ctx->tv, k); LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_rp_fold, dim3(fold_blocks(At, cb, k)), dim3(256), 0, st, At, k);
+        LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_rp_final, dim3(g_lane), dim3(64), 0, st, At, d_err); LAUNCH_CHECK();
+    return DAPOL_OK;
+}
+
 static int32_t range_prove_device(dapol_ctx* ctx, int n, int m, size_t B, const uint64_t* d_vals, const uint32_t* d_blind,
                                   const uint32_t* d_Vc, const uint32_t* d_seed, const uint64_t* d_stream, uint64_t slot_base,
                                   const uint32_t* d_tape, uint32_t* d_out, MsmTiming* tm, size_t tape_stride = 0, uint32_t sub_k = 1,
                                   size_t out_stride = 0, PendingProve* pend = nullptr) {
-    RangeArgs A{};
-    A.n = n; A.m = m; A.N = n * m;
-    A.lgN = 0;
-    while ((1 << A.lgN) < A.N) A.lgN++;
-    A.TP = 2 * A.N < 64 ? 64 : 2 * A.N;
-    A.out_words = 72 + 16 * A.lgN;
-    A.seed = d_seed; A.slot_base = slot_base;
-    A.wbits = ctx->tv.wbits; A.nwin = ctx->tv.nwin_c();
-    const size_t N = (size_t)A.N;
-    // Hybrid inner-product argument: never-fold rounds while the vectors are longer than T, then materialise the 2T
-    // folded generators once and finish on the proof's own small tables (DESIGN.md section 4.4).
-    int tail_n = 64;
-    if (ctx->opt.tail_length > 0) tail_n = ctx->opt.tail_length;
-    if (const char* e = knob("DAPOL_TAIL_N")) { int v = atoi(e); if (v == 32 || v == 64 || v == 128 || v == 256) tail_n = v; }
-    if (A.lgN < 8 || ctx->opt.tail_length < 0 || knob("DAPOL_NO_TAIL")) tail_n = 0;
-    // SHORT lists in LARGE batches (round 6): a policy's individual proofs (m = 1: 64 generators a side) and proofs of 2 ... 8 parties,
-    // batched by prove_policy_device.  The proof-stationary kernel gives such a proof a wavefront per MSM whose lanes own two terms and
-    // 255 shared doublings each (1/8 of the work is additions); swept generator-stationary (k_rp_msm_gs_hi) the batch does the 15
-    // additions per term and a Horner combine of 126 addition-equivalents per list.  From gs_small_min proofs on (DAPOL_GS_SMALL_MIN;
-    // an explicit generator_stationary option / DAPOL_GS still decides alone).
-    // (individual proofs: 1,024 / 2,048 / 4,096 proofs 5.9 / 9.1 / 16.4 ms proof-stationary, 6.2 / 6.5 / 7.0 ms swept -- profiles/r6_small_parties_sweeps.txt)
-    // (2 / 4 / 8 parties: 1,024 proofs 7.7 / 11.0 / 13.8 ms with the latency shapes, 7.2 / 8.8 / 12.3 ms swept; 4,096 proofs 21.1 / 29.4 / 38.4
-    // against 9.9 / 16.4 / 27.3 ms -- same file)
-    // (512 proofs of 4 / 8 parties: 9.7 / 11.7 ms against 8.0 / 10.5 swept; 1 and 2 parties: level or slower below the values here)
-    size_t gs_small_min = A.N == 64 ? 2048 : (A.N == 128 ? 1024 : 512);
-    if (const char* e = knob("DAPOL_GS_SMALL_MIN")) { long long v = atoll(e); if (v >= 64) gs_small_min = (size_t)v; }
-    const bool gs_small = A.N >= 64 && A.N < 1024 && A.N % 4 == 0 && B >= gs_small_min && ctx->opt.generator_stationary == 0 && !knob("DAPOL_GS");
-    // (the tail's materialisation is 2T Horner chains per proof whatever N: below 512 generators a side the remaining never-fold
-    // rounds are cheaper -- N = 256: 46 K additions against 24 K + 39 K for materialisation + tail rounds)
-    if (gs_small && A.N < 512 && !knob("DAPOL_TAIL_N")) tail_n = 0;
-    // (512 generators a side, 2^16 proofs: 373 ms with T = 64, 321 with T = 32, 400 without a tail -- same file)
-    if (gs_small && A.N == 512 && tail_n == 64 && ctx->opt.tail_length == 0 && !knob("DAPOL_TAIL_N")) tail_n = 32;
-    // Small calls (a user's proof on demand) are latency-bound: one proof per wavefront and the term range of every proof
-    // split over many wavefronts (partials summed by k_rp_sum_splits), so that a single proof keeps 64 SIMDs busy instead
-    // of a quarter of one.  Measured (tools/bench_latency.py): one 64-bit m = 32 proof in 104 ms before.
-    // With the tables' high-half rows (TableView::hi_split) a small call also halves the window steps of the main MSM -- the 238
-    // shared doublings are most of a lone wavefront's chain -- and splits down to one term per lane (64 ways); up to 32
-    // proofs then skip the tail argument (whose per-proof tables have no high-half rows: 0.66 ms per round against 0.3 ms),
-    // the materialisation is split the same way otherwise (k_rp_sum_mat), and the lane-per-proof Fiat-Shamir kernels put a
-    // proof's two point computations on two lanes (PAIR).  One height-32 padding proof: 18.6 -> 8.7 ms
-    // (profiles/r02x_latency_sweep.txt).
-    // (the latency shapes win up to where the generator-stationary sweep takes over: 5,000 / 6,144 / 7,168 proofs 16 / 21 / 30 % faster than
-    // the proof-stationary throughput shapes, 8,000 proofs level with the sweep -- profiles/r04h_small_max_probe.txt, r02_midsize_ab.txt)
-    size_t small_max = ctx->opt.small_call_max > 0 ? (size_t)ctx->opt.small_call_max : 8191;
-    if (const char* e = knob("DAPOL_SMALL_MAX")) { long long v = atoll(e); if (v >= 1) small_max = (size_t)v; }
-    // ... except where the sweep in slices (below) is faster: calls of gs_min proofs or more over at least 1,024 generators a side
-    // (1,280 / 3,072 / 4,096 / 6,144 proofs 14 / 15 / 14 / 6 % faster than the latency shapes, level at 1,024, slower at 512: profiles/r05q_gs_slices16_sweep.txt, r05r_gs_slices_forced_sweep.txt).  An explicit
-    // small_call_max / DAPOL_SMALL_MAX is taken at its word.
-    size_t gs_min = 1024;
-    if (const char* e = knob("DAPOL_GS_MIN")) { long long v = atoll(e); if (v >= 1) gs_min = (size_t)v; }
-    const bool gs_shape = A.N >= 1024 && A.N % 4 == 0 && ctx->opt.generator_stationary >= 0 && !(knob("DAPOL_GS") && atoi(knob("DAPOL_GS")) == 0);
-    if (gs_shape && ctx->opt.small_call_max <= 0 && !knob("DAPOL_SMALL_MAX") && small_max >= gs_min) small_max = gs_min - 1;
-    const bool small_call = B <= small_max && A.N >= 256 && !knob("DAPOL_LPL") && !knob("DAPOL_NO_SPLIT") && !gs_small;
-    const bool use_hi = small_call && ctx->tv.hi_split && !knob("DAPOL_NO_SMALL_HI");
-    // (DAPOL_FS_SHAPE=0/1/2 overrides; DAPOL_NO_PAIR=1 is shape 0)
-    // (mid-size calls, which have the chip to themselves, keep the shapes that shorten a proof's serial chain: 1,024 proofs 34.5 ms with
-    // a lane per proof, 32.2 with lane pairs, 31.4 with a wavefront per proof; 4,096: 91.7 / 89.5 / 92.1; 16,384: 329.6 / 327.7 / 347.4 --
-    // profiles/r05v_fs_shape_sweep.txt)
-    int fs_shape = !small_call ? (B <= 1536 ? 2 : (B <= 16384 ? 1 : 0)) : (B <= 256 ? 2 : 1);
-    if (knob("DAPOL_NO_PAIR")) fs_shape = 0;
-    if (const char* e = knob("DAPOL_FS_SHAPE")) { int v = atoi(e); if (v >= 0 && v <= 2) fs_shape = v; }
-    if (use_hi && B <= 32 && !knob("DAPOL_SMALL_TAIL")) tail_n = 0;                     // (64 proofs: 14.8 ms with the tail, 15.6 without)
-    while (tail_n && 4 * tail_n > A.N) tail_n >>= 1;             // at least two never-fold rounds before the tail
-    if (tail_n && tail_n < 32) tail_n = 0;
-    A.tail_n = tail_n;
-    int tail_lgn = 0;
-    while (tail_n && (1 << tail_lgn) < tail_n) tail_lgn++;
-    const size_t T = (size_t)tail_n;
-    // the digit matrix serves the main argument (nwin x 2N) and later the tail (TAIL_NWIN x 2T)
-    size_t dig_elems = (size_t)A.nwin * A.TP;
-    if (dig_elems < (size_t)TAIL_NWIN * 2 * T) dig_elems = (size_t)TAIL_NWIN * 2 * T;
-    // What the call can use is decided BEFORE the scratch is sized (the chunk size follows from per_proof): the coefficient tables
-    // only where an argument is short enough for them, the sweep's accumulators (69 KB per proof at 17-bit windows) only where
-    // the generator-stationary form can run at all -- individual 64-generator proofs (m = 1, the splitting policy's tail) and the
-    // latency shapes keep 17 KB per proof instead of 94 and therefore four times the chunk in the same budget.
-    const bool stab_any = ((tail_n ? A.lgN - tail_lgn : A.lgN - 1) <= STAB_ROUNDS || (tail_n && tail_lgn - 1 <= STAB_ROUNDS)) && !knob("DAPOL_NO_STAB");
-    bool gs_possible = (!small_call && A.N % 4 == 0 && A.N >= 1024 && B >= gs_min) || gs_small;
-    if (ctx->opt.generator_stationary) gs_possible = ctx->opt.generator_stationary > 0 && !small_call && A.N % 4 == 0 && A.N >= 64;
-    if (const char* e = knob("DAPOL_GS")) gs_possible = atoi(e) != 0 && !small_call && A.N % 4 == 0 && A.N >= 64;
-    // (one accumulator per list, slice, proof and window; MAT_GROUP classes of them for the materialisation.  Short lists have at
-    // most N / 32 slices, and no classes without a tail)
-    int acc_slots = GS_ACC_SLOTS;
-    if (A.N < 1024) {
-        acc_slots = 2 * (A.N / 32 < GS_MAX_SLICES ? A.N / 32 : GS_MAX_SLICES);
-        if (tail_n && acc_slots < MAT_GROUP) acc_slots = MAT_GROUP;
-    }
-    const size_t acc_bytes = gs_possible ? (size_t)acc_slots * A.nwin * 4 * FE_NL * 4 : 0;
-    const size_t stab_bytes = stab_any ? (size_t)2 * 2 * STAB_N * sizeof(sc) : 0;              // coefficient tables (two buffers x two sides)
-    const size_t per_proof = 4 * N * sizeof(sc) + dig_elems * sizeof(dig_t) + align_up(sizeof(ProofState), 16) + 3 * 160 +
-                             2 * T * TAIL_ROW_WORDS * 4 + 4 * T * sizeof(sc) + FS_PARTS_MAX * 3 * sizeof(sc) + stab_bytes + acc_bytes;
-    // ONE chunk in flight by default since round 4 (dapol_options::streams / DAPOL_STREAMS = 2..4 puts more in flight, on the
-    // context's side streams with their own shares of the scratch).  History: round 1 measured +4.8 % for two chunks in flight
-    // (the scalar-vector kernels and the Fiat-Shamir chains of one chunk under the other's MSM, profiles/r01_streams_ab.txt);
-    // with the generator-stationary sweep the two only share the chip (round 3: +0.4 %, r05g_timeline_gaps.txt), and round 4
-    // tried to give the HBM-bound kernels CUs or priority of their own -- CU-masked halves, a masked stream for the VALU-bound
-    // launches with 16 / 32 CUs left to the rest, stream priorities: every layout is slower than plain streams
-    // (profiles/r07a_stream_layout_ab.txt).  One stream with the same scratch spent on chunks of TWO rounds of resident
-    // wavefronts (131,072 proofs) instead of two chunks of one round: +0.45 % at 2^20, +0.5 % at 2^18; three rounds (153 GB)
-    // +0.7 %; one round on one stream (half the scratch) -1.6 % (profiles/r07b_one_stream_chunks_ab.txt).
-    int nlanes = ctx->opt.streams > 0 ? ctx->opt.streams : 1;
-    if (const char* e = knob("DAPOL_STREAMS")) { int v = atoi(e); if (v >= 1 && v <= 4) nlanes = v; }
-    size_t chunk = scratch_budget_bytes(ctx) / nlanes / per_proof;
-    if (chunk < 1) chunk = 1;
-    if (chunk > B) chunk = B;
-    // Launches are sized in whole "rounds" of resident wavefronts: the MSM kernels hold 3 wavefronts per SIMD
-    // (256 CUs x 4 SIMDs x 3 = 3072) and every wavefront of a launch does the same work, so a launch of k * 3072
-    // wavefronts wastes nothing on a partly filled last round.  61440 proofs = 5 rounds at 4 proofs per wavefront
-    // (main MSM), 20 rounds at one (materialisation).  Measured at 2^20 proofs (profiles/r01_chunk_ab.txt): 37.5K /
-    // 37.6K / 38.7K / 38.7K entities/s at 49152 / 60000 / 61440 / 73728.  Calls of at least 73,728 proofs use chunks of
-    // that size with 8 proofs per wavefront (3 rounds; half the shared doublings: +1.3 %, profiles/r01_lpl4_ab.txt).
-    // DAPOL_CHUNK / DAPOL_LPL override.
-    bool big_batch = false;
-    {
-        char opt_chunk[32];
-        const char* ec = knob("DAPOL_CHUNK");
-        if (!ec && ctx->opt.chunk_proofs > 0) { snprintf(opt_chunk, sizeof opt_chunk, "%lld", (long long)ctx->opt.chunk_proofs); ec = opt_chunk; }
-        // whole rounds of resident wavefronts: 16 proofs per wavefront for big calls -- as many rounds (<= 3) as the scratch holds:
-        // ONE round of 4,096 wavefronts = 65,536 proofs on MI355X (256 CUs x 4 SIMDs x 4 resident wavefronts of k_rp_msm) -- and
-        // 5 rounds at 4 proofs each otherwise
-        const size_t rw = ctx->resident_waves();
-        size_t ppw = 16;                                        // proofs per wavefront of a big call (LPL = 2; DAPOL_LPL overrides)
-        if (const char* el = knob("DAPOL_LPL")) { int v = atoi(el); if (v == 2 || v == 4 || v == 8) ppw = (size_t)(32 / v); }
-        const size_t big_chunk = (3 * rw * ppw <= chunk) ? 3 * rw * ppw : ((2 * rw * ppw <= chunk) ? 2 * rw * ppw : rw * ppw), std_chunk = 5 * rw * 4;
-        big_batch = !ec && A.N >= 1024 && B >= big_chunk && chunk >= big_chunk;
-        size_t cap = ec ? (size_t)atoll(ec) : (big_batch ? big_chunk : std_chunk);
-        // short lists: a sweep's lanes are (proof, window < 8) -- chunks of whole rounds of resident wavefronts, up to 8 of them
-        // (262,144 individual proofs: 6.5 GB of scratch)
-        const size_t small_unit = rw * 64 / (size_t)(ctx->tv.hi_split ? ctx->tv.hi_split : A.nwin);
-        if (gs_small && !ec) cap = 8 * small_unit;
-        if (cap < 64) cap = 64;
-        if (chunk > cap) chunk = cap;
-        if (gs_small && !ec && chunk > small_unit) chunk -= chunk % small_unit;
-    }
-    while (nlanes > 1 && chunk * (size_t)(nlanes - 1) >= B) nlanes--;
-    // Large calls sweep the generators instead of the proofs (kernels_range_gs.h): every wavefront of a launch reads the same
-    // tile of table rows, which therefore sits in the Infinity Cache.  DAPOL_GS=0 / 1 forces the proof-stationary / the
-    // generator-stationary form for any call that is not a small one; DAPOL_GS_TILE = rows per launch (a multiple of 4).
-    // (also below one full chunk, for proofs of at least 1,024 generators per side: one prove call of 8,192 / 16,384 / 32,768 / 49,152 proofs
-    // 23 / 6 / 11 / 11 % faster than proof-stationary, profiles/r04e_gs_midsize_sweep.txt; in slices from gs_min proofs on, see above)
-    // (what counts is the proofs per CHUNK -- the lanes of one sweep: many-party proofs get small chunks out of the scratch budget)
-    bool gs = big_batch || (!small_call && B >= gs_min && chunk >= 1024 && A.N >= 1024 && A.N % 4 == 0) || (gs_small && chunk >= 64);
-    if (ctx->opt.generator_stationary) gs = ctx->opt.generator_stationary > 0 && !small_call && A.N % 4 == 0 && A.N >= 64;
-    if (const char* e = knob("DAPOL_GS")) gs = atoi(e) != 0 && !small_call && A.N % 4 == 0 && A.N >= 64;
-    if (!gs_possible) gs = false;                            // (no accumulators were counted into the scratch)
-    const bool gs_mat = gs && tail_n && (A.N / tail_n) % 4 == 0 && !knob("DAPOL_NO_GS_MAT");
-    int gs_tile = ctx->opt.gs_tile_rows > 0 ? ctx->opt.gs_tile_rows : 16;
-    const bool gs_tile_set = ctx->opt.gs_tile_rows > 0 || knob("DAPOL_GS_TILE");
-    // DAPOL_MSM_SERIAL=1: the sweeps of all chunks in flight through ONE stream (dapol_ctx::msm_stream), one after the other, so that
-    // only the other chunks' scalar kernels run beside a sweep.  Measured and NOT the default: 53.4 K against 54.6 K entities/s at
-    // 2^20 (profiles/r04a_msm_serial_ab.txt) -- two sweeps side by side lose less than the pipeline bubbles of one at a time.
-    bool msm_serial_want = false;
-    if (const char* e = knob("DAPOL_MSM_SERIAL")) msm_serial_want = atoi(e) != 0;
-    if (const char* e = knob("DAPOL_GS_TILE")) { int v = atoi(e); if (v >= 4 && v % 4 == 0) gs_tile = v; }
-    // A sweep's lanes are (proof, window).  A chunk that has the chip to itself (calls of up to one chunk; the ragged last chunk of a
-    // call) sweeps each list in SLICES side by side (k_rp_msm_gs, gridDim.y): a few thousand proofs alone would leave every SIMD a
-    // lone wavefront walking its additions one table-lookup latency at a time, and up to ~50,000 the launches are so few wavefront
-    // rounds long that the partly filled last round shows (7,680 wavefronts = 1.9 rounds at 32,768 proofs); few lanes also look a
-    // table row up only a few times, so there is no tile worth keeping in the Infinity Cache.  One prove call of 4,096 / 8,192 /
-    // 16,384 / 32,768 / 49,152 proofs: 107.9 / 184.8 / 336.4 / 632.2 / 940.4 ms unsliced, 90.8 / 174.2 / 324.5 / 616.0 / 918.7 ms in 16 / 16 / 8 / 8 / 4
-    // slices; 65,536: no difference (profiles/r05r_gs_slices_forced_sweep.txt, r05s_gs_slices_sweep.txt).  Full chunks stay whole: their tile lives in the Infinity Cache and the other chunk
-    // in flight fills the rounds.  dapol_options::gs_slices / DAPOL_GS_SLICES overrides (1, 2, 4, 8, 16).
-    int gs_slices_forced = (ctx->opt.gs_slices > 0 && A.N % (4 * ctx->opt.gs_slices) == 0 && A.N / ctx->opt.gs_slices >= 4) ? ctx->opt.gs_slices : 0;
-    if (const char* e = knob("DAPOL_GS_SLICES")) { int v = atoi(e); if ((v == 1 || v == 2 || v == 4 || v == 8 || v == 16) && A.N % (4 * v) == 0 && A.N / v >= 4) gs_slices_forced = v; }
-    // Short lists (fewer than 1,024 generators a side) are swept with two lookups per term where the tables have high-half rows:
-    // LW = hi_split window sums per list instead of nwin (k_rp_msm_gs_hi; DAPOL_NO_GS_HI=1: the plain sweep).
-    const int gs_LW = (gs && A.N < 1024 && ctx->tv.hi_split && !knob("DAPOL_NO_GS_HI")) ? ctx->tv.hi_split : A.nwin;
-    auto gs_slices_for = [&](size_t cb) {
-        // (a forced count never exceeds the accumulator slots the scratch was sized for: short lists have 2 x min(N / 32, 16) of them)
-        if (gs_slices_forced) return gs_slices_forced <= acc_slots / 2 ? gs_slices_forced : acc_slots / 2;
-        int ns = cb <= 4096 ? 16 : (cb < 40000 ? 8 : (cb < 65536 ? 4 : 1));
-        if (A.N < 1024) {                                   // by lanes: slices while one list's lanes do not fill the chip twice over
-            const size_t lanes = cb * (size_t)gs_LW;
-            ns = lanes >= 2 * (size_t)GS_FULL_LANES ? 1 : (lanes >= (size_t)GS_FULL_LANES ? 2 : (lanes >= (size_t)GS_FULL_LANES / 2 ? 4 : (lanes >= (size_t)GS_FULL_LANES / 8 ? 8 : 16)));
-        }
-        while (ns > 1 && ((A.N / ns) % 4 != 0 || A.N / ns < 32)) ns /= 2;
-        return ns;
-    };
-    int msm_split = 1, mat_split = 1;
-    if (small_call) {
-        const int cap = small_split_cap(use_hi), min_terms = use_hi ? 1 : 4;
-        while (msm_split < cap && (size_t)msm_split * 2 * B <= 2048 && A.N / 32 / (msm_split * 2) >= min_terms) msm_split *= 2;
-        if (tail_n && !knob("DAPOL_NO_SPLIT_MAT"))
-            while (mat_split < 8 && (size_t)(mat_split * 2) * B * (size_t)(tail_n / 32) <= 4096 && A.N / tail_n / (mat_split * 2) >= 2) mat_split *= 2;
-    }
-    A.use_hi = use_hi ? 1 : 0;
-    // ... and the two 2N-position scalar phases (k_rp_poly, k_rp_lr) are walked by up to 8 wavefronts per proof instead of one
-    A.fs_parts = 1;
-    if (small_call && B <= 64 && !knob("DAPOL_NO_FS_PARTS")) {
-        const int iters = (A.N + 63) / 64;
-        while (A.fs_parts < FS_PARTS_MAX && iters / (A.fs_parts * 2) >= 2) A.fs_parts *= 2;
-    }
-    // ... and with one point per four lanes when the proofs are few enough for 4x the wavefronts (DAPOL_NO_QUAD=1: lane kernel)
-    int quad_split = 0;
-    // Four lanes per point is 1.5x the work per point: it pays while the launch is a lone wavefront's chain, up to about 8 proofs
-    // (profiles/r02_midsize_ab.txt: 8 proofs 6.5 against 6.8 ms, 16 proofs 8.9 against 6.9).
-    if (use_hi && msm_split > 1 && (size_t)msm_split * 4 * B <= quad_max_waves(2048) && A.N % (8 * msm_split * 4) == 0 && !knob("DAPOL_NO_QUAD")) quad_split = msm_split * 4;
-    const int part_split = quad_split ? quad_split : msm_split;
-    const size_t split_bytes = (part_split > 1 ? align_up(2 * chunk * (size_t)part_split * 160, 256) : 0) +
-                               (mat_split > 1 ? align_up(chunk * 2 * T * (size_t)mat_split * 160, 256) : 0);
+    ProveShape s{};
+    s.n = n; s.m = m; s.B = B;
+    s.tail_length = ctx->opt.tail_length; s.small_call_max = ctx->opt.small_call_max; s.generator_stationary = ctx->opt.generator_stationary;
+    s.streams = ctx->opt.streams; s.gs_tile_rows = ctx->opt.gs_tile_rows; s.gs_slices = ctx->opt.gs_slices; s.chunk_proofs = ctx->opt.chunk_proofs;
+    s.wbits = ctx->tv.wbits; s.nwin = ctx->tv.nwin_c(); s.hi_split = ctx->tv.hi_split;
+    s.n_cu = ctx->n_cu; s.resident_waves = ctx->resident_waves();
+    s.budget_bytes = scratch_budget_bytes(ctx);
+    s.timed = tm != nullptr;
+    ProvePlan P = plan_range_prove(s);
     // The budget is a wish, the device's free memory the fact: on an allocation failure fall back to one chunk in flight,
     // then to smaller chunks, before giving up.
-    size_t lane_bytes = align_up(chunk * per_proof + 8192 + split_bytes, 4096);
-    for (;;) {
-        hipError_t e = ctx->scratch.ensure(lane_bytes * nlanes);
-        if (e == hipSuccess) break;
-        (void)hipGetLastError();
-        if (e != hipErrorOutOfMemory || (nlanes == 1 && chunk <= 64)) return fail_hip(e, "scratch allocation", __LINE__);
-        if (nlanes > 1) nlanes--;
-        else chunk = (chunk + 1) / 2;
-        lane_bytes = align_up(chunk * per_proof + 8192 + split_bytes, 4096);
-    }
-    RangeArgs lane_args[4];
-    int32_t* lane_split[4][3];
-    int32_t* lane_gsacc[4];
-    hipStream_t lane_stream[4] = {ctx->stream, ctx->side[0], ctx->side[1], ctx->side[2]};
-    // DAPOL_STREAM_LAYOUT (measurement knob, ensure_stream_layout): the two chunks in flight on CU-masked / prioritised streams
-    bool laid = false;
-    struct LayoutSync { bool on = false; ~LayoutSync() { if (on) (void)hipDeviceSynchronize(); } } layout_sync;
-    if (const char* e = knob("DAPOL_STREAM_LAYOUT")) {
-        if (gs && nlanes == 2) {
-            int32_t rc = ensure_stream_layout(ctx, e);
-            if (rc) return rc;
-            lane_stream[0] = ctx->layout_lane[0]; lane_stream[1] = ctx->layout_lane[1];
-            laid = layout_sync.on = true;
+    for (bool lowered = false;; lowered = true) {
+        hipError_t e = ctx->scratch.ensure(P.lane_bytes() * P.nlanes);
+        if (e == hipSuccess) {
+            if (lowered) P.finalise(s, P.chunk, P.nlanes);    // (the lanes per list follow from the chunk that fitted)
+            break;
         }
+        (void)hipGetLastError();
+        if (e != hipErrorOutOfMemory || (P.nlanes == 1 && P.chunk <= 64)) return fail_hip(e, "scratch allocation", __LINE__);
+        if (P.nlanes > 1) P.nlanes--;
+        else P.chunk = (P.chunk + 1) / 2;
     }
-    const bool split_msm = laid && ctx->layout_split_msm;
-    for (int ln = 0; ln < nlanes; ln++) {
-        uint8_t* base = (uint8_t*)ctx->scratch.p + lane_bytes * ln;
-        size_t o = 0;
-        A.a = (sc*)(base + o); o += chunk * N * sizeof(sc);
-        A.b = (sc*)(base + o); o += chunk * N * sizeof(sc);
-        A.s1 = (sc*)(base + o); o += chunk * N * sizeof(sc);
-        A.s2 = (sc*)(base + o); o += chunk * N * sizeof(sc);
-        A.dig = (dig_t*)(base + o); o += align_up(chunk * dig_elems * sizeof(dig_t), 256);
-        A.st = (ProofState*)(base + o); o += align_up(chunk * sizeof(ProofState), 256);
-        A.PA = (int32_t*)(base + o); o += chunk * 160;
-        A.P0 = (int32_t*)(base + o); o += chunk * 160;
-        A.P1 = (int32_t*)(base + o); o += chunk * 160;
-        A.tailT = (int32_t*)(base + o); o += chunk * 2 * T * TAIL_ROW_WORDS * 4;
-        A.tail_a = (sc*)(base + o); o += chunk * T * sizeof(sc);
-        A.tail_b = (sc*)(base + o); o += chunk * T * sizeof(sc);
-        A.tail_s1 = (sc*)(base + o); o += chunk * T * sizeof(sc);
-        A.tail_s2 = (sc*)(base + o); o += chunk * T * sizeof(sc);
-        A.fs_part = (sc*)(base + o); o += chunk * FS_PARTS_MAX * 3 * sizeof(sc);
-        A.stab = stab_bytes ? (sc*)(base + o) : nullptr; o += chunk * stab_bytes;
-        lane_gsacc[ln] = (int32_t*)(base + o); o += chunk * acc_bytes;
-        o = align_up(o, 256);
-        // (the split buffers stay LAST: split_bytes only counts them when a split is in use)
-        lane_split[ln][0] = (int32_t*)(base + o); o += chunk * (size_t)part_split * 160;
-        lane_split[ln][1] = (int32_t*)(base + o); o += chunk * (size_t)part_split * 160;
-        o = align_up(o, 256);
-        lane_split[ln][2] = (int32_t*)(base + o); o += mat_split > 1 ? chunk * 2 * T * (size_t)mat_split * 160 : 0;
-        lane_args[ln] = A;
-    }
-    const int nf_rounds = A.lgN - tail_lgn;
-    int lpl = msm_lanes_per_list(A.N, big_batch), tail_lpl = tail_lanes_per_list(small_call);
-    if (small_call) lpl = 32;
-    else if (!knob("DAPOL_LPL") && A.N >= 1024 && !big_batch && chunk < 32768) {    // mid-size calls; large ones keep the measured defaults
-        // (one proof per wavefront is not a candidate: with 64 different table rows per lookup instruction the kernel runs at half the
-        // rate per addition of 32 or fewer -- 2,048 proofs 98 -> 63 ms, 4,096 proofs 190 -> 114 ms, profiles/r02_midsize_ab.txt)
-        const int cand[2] = {8, 16};
-        lpl = pick_lanes_per_list(chunk, A.N, A.nwin, A.wbits, cand, 2, ctx->resident_waves(), (size_t)ctx->n_cu * 4);
-    }
-    if (!knob("DAPOL_TAIL_LPL") && !small_call && tail_n && chunk < 65536) {             // (a chunk that has the chip to itself; full chunks: 2, measured)
-        const int cand[4] = {2, 4, 8, 32};
-        tail_lpl = pick_lanes_per_list(chunk, tail_n, TAIL_NWIN, TAIL_WBITS, cand, 4, ctx->resident_waves(), (size_t)ctx->n_cu * 4, true);
-    }
-    // Coefficient tables instead of per-round s-vector updates (kernels_range.h, RangeArgs::stab) wherever the argument needs at
-    // most TG_6: the main argument when a tail follows within six rounds (or is that short itself), the tail argument up to T = 128.
-    const int nf_rounds_ = A.lgN - tail_lgn;
-    const bool stab_main = stab_any && (tail_n ? nf_rounds_ : A.lgN - 1) <= STAB_ROUNDS;
-    const bool stab_tail = stab_any && tail_n && tail_lgn - 1 <= STAB_ROUNDS;
-    for (int ln = 0; ln < nlanes; ln++) lane_args[ln].mat_round = nf_rounds_;
+    const size_t chunk = P.chunk, slots = (size_t)m * (2 * (size_t)n + 4);
+    const int nlanes = P.nlanes;
+    RangeArgs A{};                                           // what every chunk of the call shares
+    A.n = n; A.m = m; A.N = P.N; A.lgN = P.lgN; A.TP = P.TP;
+    A.out_words = 72 + 16 * A.lgN;
+    A.seed = d_seed; A.slot_base = slot_base;
+    A.wbits = s.wbits; A.nwin = s.nwin;
+    A.tail_n = P.tail_n; A.use_hi = P.use_hi ? 1 : 0; A.fs_parts = P.fs_parts; A.mat_round = P.nf_rounds();
+    A.stream_id = d_stream;                                  // (row-indexed from the call's first proof: RangeArgs::p0)
+    A.tape_stride = (uint32_t)(tape_stride ? tape_stride : slots);
+    A.tape = d_tape;
+    A.sub_k = sub_k ? sub_k : 1; A.sub_slots = (uint32_t)slots;
+    A.out = d_out; A.out_stride = out_stride ? out_stride : (size_t)A.out_words;
+    ProveLane lanes[4];
+    hipStream_t lane_stream[4] = {ctx->stream, ctx->side[0], ctx->side[1], ctx->side[2]};
+    for (int ln = 0; ln < nlanes; ln++) lanes[ln] = carve_lane(P, A, (uint8_t*)ctx->scratch.p + P.lane_bytes() * ln);
     DevBuf<uint32_t> err_own;
     DevBuf<uint32_t>& err = pend ? pend->err : err_own;
     HIPCHK(err.alloc(1));
@@ -479,214 +380,36 @@ static int32_t range_prove_device(dapol_ctx* ctx, int n, int m, size_t B, const 
     ForkGuard fg(ctx);                                       // an early return below waits for the chunks in flight on the side streams
     if (nlanes > 1) {                                        // the side streams start after everything already queued on the first
         HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-        for (int ln = laid ? 0 : 1; ln < nlanes; ln++) { HIPCHK(hipStreamWaitEvent(lane_stream[ln], ctx->ev_fork, 0)); if (!laid) fg.forked(ln - 1); }
+        for (int ln = 1; ln < nlanes; ln++) { HIPCHK(hipStreamWaitEvent(lane_stream[ln], ctx->ev_fork, 0)); fg.forked(ln - 1); }
     }
-    unsigned producer_waves = 0;                              // DAPOL_PRODUCER_WAVES (measurement knob): cap on the grid of the *_gs producers
-    if (const char* e = knob("DAPOL_PRODUCER_WAVES")) { long v = atol(e); if (v >= 64) producer_waves = (unsigned)v; }
-    const size_t slots = (size_t)m * (2 * (size_t)n + 4);
-    const bool msm_serial = (msm_serial_want || split_msm) && gs && nlanes > 1;
-    hipStream_t const msm_stream = split_msm ? ctx->layout_msm : ctx->msm_stream;
-    if (msm_serial) fg.also(msm_stream);                     // (measurement knobs only) its sweeps read the chunks' scratch: an early return waits for it too
-    hipError_t hop_err = hipSuccess;                         // first failure of an event record / wait that orders msm_stream against a chunk's stream
-    auto hopchk = [&](hipError_t e) { if (e != hipSuccess && hop_err == hipSuccess) hop_err = e; };
-#define HOP_CHECK() do { if (hop_err != hipSuccess) return fail_hip(hop_err, "event hop between a chunk's stream and the MSM stream", __LINE__); } while (0)
     size_t chunk_no = 0;
     for (size_t first = 0; first < B; first += chunk, chunk_no++) {
         const int ln = (int)(chunk_no % (size_t)nlanes);
-        hipStream_t st = lane_stream[ln];
         if (chunk_no == 2) FAULT_AFTER_FORK("prove_lanes");     // (chunk 1 is in flight on a side stream)
-        RangeArgs A = lane_args[ln];                            // (shadows the template above: this chunk's pointers)
-        sc* const stab_buf = A.stab;
-        if (!stab_main) A.stab = nullptr;
-        size_t cb = B - first < chunk ? B - first : chunk;
-        A.B = cb;
-        A.vals = d_vals + first * m;
-        A.blind = d_blind + first * m * 8;
-        A.Vc = d_Vc + first * m * 8;
-        A.stream_id = d_stream;                                 // (row-indexed from the call's first proof: RangeArgs::p0)
-        A.tape_stride = (uint32_t)(tape_stride ? tape_stride : slots);
-        A.tape = d_tape;
-        A.p0 = first; A.sub_k = sub_k ? sub_k : 1; A.sub_slots = (uint32_t)slots;
-        A.out = d_out; A.out_stride = out_stride ? out_stride : (size_t)A.out_words;
-        const unsigned g_wave = (unsigned)cb, g_lane = nblk(cb, 64), g_dig = (unsigned)(cb * (size_t)(A.TP / 64));
-        auto main_msm = [&](int round) {                      // the fixed-base MSM of one round, split or not
-            if (gs) {                                         // large calls: sweep the generators, a tile of rows per launch
-                const unsigned g_acc = nblk(cb * (size_t)gs_LW, 64);
-                hipStream_t ms = msm_serial ? msm_stream : st;
-                if (msm_serial) { hopchk(hipEventRecord(ctx->ev_msm_pre[ln], st)); hopchk(hipStreamWaitEvent(ms, ctx->ev_msm_pre[ln], 0)); }
-                // calls of a few thousand proofs: gs_slices slices of each list side by side (lanes enough to fill the chip)
-                const int ns = gs_slices_for(cb);
-                const int slice_rows = A.N / ns;
-                // (few lanes look a row up about once per entry -- there is no tile to keep in the Infinity Cache: longer launches, fewer of them;
-                // 8,192 / 12,288 / 16,384 proofs 2-3 % faster with 32 rows, full chunks 1 % slower: profiles/r05o_gs_slices_sweep.txt, r03f_gs_ab_2e20.txt)
-                int tile = (!gs_tile_set && cb * (size_t)A.nwin < 2 * (size_t)GS_FULL_LANES && slice_rows >= 32) ? 32 : gs_tile;
-                // (two table rows per term: half the terms per launch keep the tile the same 134 MB)
-                if (gs_LW < A.nwin && !gs_tile_set) tile = tile / 2;
-                const size_t side_words = (size_t)4 * FE_NL * cb * gs_LW * ns;      // the two lists' accumulators, one after the other
-                for (int side = 0; side < 2; side++)
-                    for (int q0 = 0; q0 < slice_rows; q0 += tile) {
-                        const int nq = slice_rows - q0 < tile ? slice_rows - q0 : tile;
-                        if (gs_LW < A.nwin)
-                            hipLaunchKernelGGL(k_rp_msm_gs_hi, dim3(g_acc, ns), dim3(64), ctx->msm_dyn_lds, ms, A, ctx->tv, round, side, q0, nq, q0 == 0 ? 1 : 0,
-                                               lane_gsacc[ln] + side * side_words, slice_rows, gs_LW);
-                        else
-                            hipLaunchKernelGGL(k_rp_msm_gs, dim3(g_acc, ns), dim3(64), ctx->msm_dyn_lds, ms, A, ctx->tv, round, side, q0, nq, q0 == 0 ? 1 : 0,
-                                               lane_gsacc[ln] + side * side_words, slice_rows);
-                    }
-                if (ns > 1) hipLaunchKernelGGL(k_rp_gs_sum_slices, dim3(nblk(2 * cb * (size_t)gs_LW, 64)), dim3(64), 0, ms, A, lane_gsacc[ln], side_words, ns, gs_LW);
-                hipLaunchKernelGGL(k_rp_gs_combine, dim3(nblk(2 * cb, 64)), dim3(64), 0, ms, A, lane_gsacc[ln], side_words, ns, gs_LW);
-                if (msm_serial) { hopchk(hipEventRecord(ctx->ev_msm_post[ln], ms)); hopchk(hipStreamWaitEvent(st, ctx->ev_msm_post[ln], 0)); }
-                if (tm) tm->count(0, 2 * (size_t)((slice_rows + tile - 1) / tile));
-            } else if (quad_split) {                                 // a few proofs: one point per four lanes (k_rp_msm_quad)
-                RangeArgs As = A;
-                As.nsplit = quad_split; As.P0 = lane_split[ln][0]; As.P1 = lane_split[ln][1];
-                hipLaunchKernelGGL(k_rp_msm_quad, dim3((unsigned)(cb * (size_t)quad_split)), dim3(64), 0, st, As, ctx->tv, round);
-                hipLaunchKernelGGL(k_rp_sum_splits, dim3((unsigned)(2 * cb)), dim3(64), 0, st, cb, quad_split, As.P0, As.P1, A.P0, A.P1);
-            } else if (msm_split > 1) {
-                RangeArgs As = A;
-                As.nsplit = msm_split; As.P0 = lane_split[ln][0]; As.P1 = lane_split[ln][1];
-                launch_msm(st, As, ctx->tv, round, lpl, ctx->msm_dyn_lds);
-                hipLaunchKernelGGL(k_rp_sum_splits, dim3((unsigned)(2 * cb)), dim3(64), 0, st, cb, msm_split, As.P0, As.P1, A.P0, A.P1);
-            } else {
-                launch_msm(st, A, ctx->tv, round, lpl, ctx->msm_dyn_lds);
-                if (tm) tm->count(0, 1);
-            }
-        };
-        hipLaunchKernelGGL(k_rp_nonce_key, dim3(g_lane), dim3(64), 0, st, A); LAUNCH_CHECK();
-        unsigned g_gsdig = nblk(cb * (size_t)(2 * A.N), 64);                    // generator-stationary producers: a thread per term
-        if (producer_waves && g_gsdig > producer_waves) g_gsdig = producer_waves;   // (experiment: fewer blocks, each walking several)
-        if (gs) hipLaunchKernelGGL(k_rp_nonces_gs, dim3(g_gsdig), dim3(64), 0, st, A);
-        else hipLaunchKernelGGL(k_rp_nonces, dim3(g_dig), dim3(64), 0, st, A);
-        LAUNCH_CHECK();
-        // a small call's A commitment (a chain of additions on one wavefront) runs beside the S commitment's MSM
-        const bool side_A = small_call && nlanes == 1 && B <= 64 && !tm && !knob("DAPOL_NO_SIDE_A");
-        if (side_A) {
-            HIPCHK(hipEventRecord(ctx->ev_fork, st));
-            HIPCHK(hipStreamWaitEvent(ctx->side[2], ctx->ev_fork, 0));
-            fg.forked(2);
-            hipLaunchKernelGGL(k_rp_A, dim3(g_wave), dim3(64), 0, ctx->side[2], A, ctx->tv); LAUNCH_CHECK();
-            HIPCHK(hipEventRecord(ctx->ev_join[2], ctx->side[2]));
-            FAULT_AFTER_FORK("prove_A");
-        } else if (gs && A.N < 1024 && cb >= 4096 && !knob("DAPOL_NO_A_LANE")) {      // short proofs in bulk: a lane per proof (k_rp_A_lane)
-            hipLaunchKernelGGL(k_rp_A_lane, dim3(g_lane), dim3(64), 0, st, A, ctx->tv); LAUNCH_CHECK();
-        } else {
-            hipLaunchKernelGGL(k_rp_A, dim3(g_wave), dim3(64), 0, st, A, ctx->tv); LAUNCH_CHECK();
-        }
-        if (tm) HIPCHK(tm->mark(st));
-        main_msm(-1); LAUNCH_CHECK(); HOP_CHECK();
-        if (tm) HIPCHK(tm->mark(st));
-        if (side_A) { HIPCHK(hipStreamWaitEvent(st, ctx->ev_join[2], 0)); fg.joined(2); }
-        LAUNCH_FS(k_rp_finish1, fs_shape, cb, st, A, ctx->tv); LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_rp_poly, dim3(g_wave * (unsigned)A.fs_parts), dim3(64), 0, st, A); LAUNCH_CHECK();
-        LAUNCH_FS(k_rp_finish2, fs_shape, cb, st, A, ctx->tv); LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_rp_lr, dim3(g_wave * (unsigned)A.fs_parts), dim3(64), 0, st, A); LAUNCH_CHECK();
-        if (fs_shape == 2) hipLaunchKernelGGL(k_rp_finish3<2>, dim3(g_wave), dim3(64), 0, st, A);
-        else hipLaunchKernelGGL(k_rp_finish3<0>, dim3(g_lane), dim3(64), 0, st, A);
-        LAUNCH_CHECK();
-        for (int k = 0; k < nf_rounds; k++) {
-            if (gs) hipLaunchKernelGGL(k_rp_round_prep_gs, dim3(g_gsdig), dim3(64), 0, st, A, k);
-            else hipLaunchKernelGGL(k_rp_round_prep, dim3(g_dig), dim3(64), 0, st, A, k);
-            LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_rp_round_ip, dim3(g_wave), dim3(64), 0, st, A, k); LAUNCH_CHECK();
-            if (tm) HIPCHK(tm->mark(st));
-            main_msm(k); LAUNCH_CHECK(); HOP_CHECK();
-            if (tm) HIPCHK(tm->mark(st));
-            LAUNCH_FS(k_rp_round_finish, fs_shape, cb, st, A, ctx->tv, k); LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_rp_fold, dim3(fold_blocks(A, cb, k)), dim3(256), 0, st, A, k);
-            LAUNCH_CHECK();
-        }
-        if (nf_rounds < A.lgN) {
-            if (gs_mat) hipLaunchKernelGGL(k_rp_mat_prep_gs, dim3(g_gsdig), dim3(64), 0, st, A);
-            else hipLaunchKernelGGL(k_rp_mat_prep, dim3(g_dig), dim3(64), 0, st, A);
-            LAUNCH_CHECK();
-            if (tm) HIPCHK(tm->mark(st, 1));
-            const unsigned g_tail = (unsigned)(cb * (size_t)(tail_n / 32));
-            if (gs_mat) {                                     // a class (one folded generator of every proof) per tile, MAT_GROUP classes per Horner launch
-                hipStream_t ms = msm_serial ? msm_stream : st;
-                if (msm_serial) { HIPCHK(hipEventRecord(ctx->ev_msm_pre[ln], st)); HIPCHK(hipStreamWaitEvent(ms, ctx->ev_msm_pre[ln], 0)); }
-                const int LW = ctx->tv.hi_split ? ctx->tv.hi_split : A.nwin;
-                const unsigned g_cls = nblk(cb * (size_t)LW, 64);
-                const size_t slot_words = (size_t)4 * FE_NL * cb * LW;
-                int cpl = 1;
-                while (cpl < MAT_GROUP && cb * (size_t)LW * (size_t)cpl < GS_FULL_LANES) cpl *= 2;
-                if (const char* e = knob("DAPOL_GS_MAT_CPL")) { int v = atoi(e); if (v >= 1 && v <= MAT_GROUP) cpl = v; }
-                for (int side = 0; side < 2; side++)
-                    for (int c0 = 0; c0 < tail_n; c0 += MAT_GROUP) {
-                        const int nc = tail_n - c0 < MAT_GROUP ? tail_n - c0 : MAT_GROUP;
-                        for (int c = 0; c < nc; c += cpl) {               // cpl classes per launch (1 when one class's lanes fill the chip)
-                            const int ny = nc - c < cpl ? nc - c : cpl;
-                            hipLaunchKernelGGL(k_rp_mat_gs, dim3(g_cls, ny), dim3(64), ctx->msm_dyn_lds, ms, A, ctx->tv, side, c0 + c, 0, LW, lane_gsacc[ln] + c * slot_words);
-                            if (LW < A.nwin) hipLaunchKernelGGL(k_rp_mat_gs, dim3(g_cls, ny), dim3(64), ctx->msm_dyn_lds, ms, A, ctx->tv, side, c0 + c, 1, LW, lane_gsacc[ln] + c * slot_words);
-                        }
-                        hipLaunchKernelGGL(k_rp_mat_gs_horner, dim3(nblk(cb * (size_t)nc, 64)), dim3(64), 0, ms, A, side, c0, nc, LW, lane_gsacc[ln]);
-                    }
-                if (msm_serial) { HIPCHK(hipEventRecord(ctx->ev_msm_post[ln], ms)); HIPCHK(hipStreamWaitEvent(st, ctx->ev_msm_post[ln], 0)); }
-                if (tm) tm->count(1, 2 * (size_t)((tail_n + cpl - 1) / cpl) * (LW < A.nwin ? 2 : 1));
-            } else if (mat_split > 1) {
-                RangeArgs Am = A;
-                Am.nsplit = mat_split; Am.P0 = lane_split[ln][2];
-                hipLaunchKernelGGL((k_rp_msm<MSM_MATERIALIZE, 32>), dim3(g_tail * (unsigned)mat_split), dim3(64), 0, st, Am, ctx->tv, -1); LAUNCH_CHECK();
-                hipLaunchKernelGGL(k_rp_sum_mat, dim3(nblk(cb * 2 * T, 64)), dim3(64), 0, st, cb * 2 * T, mat_split, Am.P0, A.tailT);
-            } else {
-                hipLaunchKernelGGL((k_rp_msm<MSM_MATERIALIZE, 32>), dim3(g_tail), dim3(64), 0, st, A, ctx->tv, -1);
-                if (tm) tm->count(1, 1);
-            }
-            LAUNCH_CHECK();
-            if (tm) HIPCHK(tm->mark(st, 1));
-            // (stream layouts that separate the VALU-bound launches also move the tail's tables and MSMs over)
-            hipStream_t const ts = (split_msm && msm_serial) ? msm_stream : st;
-            auto hop = [&](hipStream_t from, hipStream_t to, hipEvent_t ev) { if (from != to) { hopchk(hipEventRecord(ev, from)); hopchk(hipStreamWaitEvent(to, ev, 0)); } };
-            {
-                RangeArgs Ai = A;
-                Ai.stab = stab_tail ? stab_buf : nullptr;         // (k_rp_tail_table also resets the tables for the tail argument)
-                hop(st, ts, ctx->ev_msm_pre[ln]);
-                hipLaunchKernelGGL(k_rp_tail_table, dim3(g_tail), dim3(64), 0, ts, Ai); LAUNCH_CHECK();
-                hop(ts, st, ctx->ev_msm_post[ln]);
-            }
-            // The remaining rounds: the same never-fold kernels on the length-T argument over the proof's own table.
-            RangeArgs At = A;
-            At.N = tail_n; At.lgN = tail_lgn; At.TP = 2 * tail_n; At.wbits = TAIL_WBITS; At.nwin = TAIL_NWIN; At.nsplit = 0;
-            At.a = A.tail_a; At.b = A.tail_b; At.s1 = A.tail_s1; At.s2 = A.tail_s2;
-            At.stab = stab_tail ? stab_buf : nullptr;
-            At.out_round0 = nf_rounds;
-            const TableView tvt{A.tailT, 1, TAIL_WBITS, 0, 0};
-            for (int k = 0; k < tail_lgn; k++) {
-                hipLaunchKernelGGL(k_rp_round_prep, dim3(g_tail), dim3(64), 0, st, At, k); LAUNCH_CHECK();
-                hipLaunchKernelGGL(k_rp_round_ip, dim3(g_wave), dim3(64), 0, st, At, k); LAUNCH_CHECK();
-                hop(st, ts, ctx->ev_msm_pre[ln]);
-                launch_msm_tail(ts, At, tvt, k, tail_lpl); LAUNCH_CHECK();
-                hop(ts, st, ctx->ev_msm_post[ln]);
-                HOP_CHECK();
-                LAUNCH_FS(k_rp_round_finish, fs_shape, cb, st, At, ctx->tv, k); LAUNCH_CHECK();
-                hipLaunchKernelGGL(k_rp_fold, dim3(fold_blocks(At, cb, k)), dim3(256), 0, st, At, k);
-                LAUNCH_CHECK();
-            }
-            hipLaunchKernelGGL(k_rp_final, dim3(g_lane), dim3(64), 0, st, At, err.p); LAUNCH_CHECK();
-        } else {
-            hipLaunchKernelGGL(k_rp_final, dim3(g_lane), dim3(64), 0, st, A, err.p); LAUNCH_CHECK();
-        }
+        RangeArgs Ac = lanes[ln].A;                             // this chunk: the lane's buffers, its slice of the inputs
+        Ac.B = B - first < chunk ? B - first : chunk;
+        Ac.vals = d_vals + first * m;
+        Ac.blind = d_blind + first * m * 8;
+        Ac.Vc = d_Vc + first * m * 8;
+        Ac.p0 = first;
+        int32_t rc = queue_chunk(ctx, P, lanes[ln], Ac, lane_stream[ln], fg, err.p, tm);
+        if (rc) return rc;
     }
-    for (int ln = laid ? 0 : 1; ln < nlanes; ln++) {         // join: the first stream continues after the others have drained
-        hipEvent_t ev = laid ? ctx->layout_ev[ln] : ctx->ev_join[ln - 1];
-        HIPCHK(hipEventRecord(ev, lane_stream[ln]));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ev, 0));
-        if (!laid) fg.joined(ln - 1);
+    for (int ln = 1; ln < nlanes; ln++) {                    // join: the first stream continues after the others have drained
+        HIPCHK(hipEventRecord(ctx->ev_join[ln - 1], lane_stream[ln]));
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[ln - 1], 0));
+        fg.joined(ln - 1);
     }
     if (pend) {                                              // queued, not awaited: the caller finishes (PendingProve::finish)
-        HOP_CHECK();
         pend->ctx = ctx;
         pend->h_err_p = ctx->h_pinned + pend->pinned_slot;
         HIPCHK(hipMemcpyAsync(pend->h_err_p, err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
         pend->armed = true;
-        fg.done();
         return DAPOL_OK;
     }
     uint32_t h_err = 0;
     HIPCHK(hipMemcpyAsync(&h_err, err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HOP_CHECK();
-    fg.done();                                               // (everything on the MSM stream was ordered before the chunks' streams, which have drained)
-#undef HOP_CHECK
     if (h_err) return fail(DAPOL_ERR_INVALID_ARGUMENT, "prover drew a zero challenge (ProofError::MaliciousDealer)");
     return DAPOL_OK;
 }

@@ -33,13 +33,13 @@ static bool verify_wave_transcript(int m) {
     if (const char* e = knob("DAPOL_VERIFY_WAVE_TRANSCRIPT")) return atoi(e) != 0;
     return m >= 256;
 }
-// queue_only: a call of ONE chunk returns with its work queued on ctx's stream, without the host wait at the end (the groups of a
-// small call's plan on lanes of their own, verify_policy_device).
 static size_t verify_rlc_min(const dapol_ctx* ctx) {          // fewest proofs that are checked as ONE random linear combination
     size_t rlc_min = ctx->opt.verify_batch_min >= 2 ? (size_t)ctx->opt.verify_batch_min : RLC_MIN_DEFAULT;
     if (const char* e = knob("DAPOL_VERIFY_RLC_MIN")) { long v = atol(e); if (v >= 2) rlc_min = (size_t)v; }
     return rlc_min;
 }
+// queue_only: a call of ONE chunk returns with its work queued on ctx's stream, without the host wait at the end (the groups of a
+// small call's plan on lanes of their own, verify_policy_device).
 static int32_t range_verify_device(dapol_ctx* ctx, int n_bits, int m, size_t b, const uint32_t* d_proofs, size_t stride_words,
                                    const uint32_t* d_V, const uint32_t* d_seed, uint8_t* d_ok, bool queue_only = false) {
     hipStream_t st = ctx->stream;

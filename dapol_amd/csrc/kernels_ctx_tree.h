@@ -255,7 +255,7 @@ struct PadTape {
     uint32_t n_draws;
     uint32_t* short_flag;      // set when the tree needs more draws than the tape holds
 };
-// SPLIT = 1 (round 6 experiment, DAPOL_TREE_SPLIT=1): the padding children of the level were made by k_tree_pad_level just before --
+// SPLIT = 1 (the default since round 6; DAPOL_TREE_SPLIT=0 turns it off): the padding children of the level were made by k_tree_pad_level just before --
 // their records are read from padC / padH / padr and their points from extpad[q] -- so that neither kernel holds a fixed-base
 // product, two encodings and three hashes in one register allocation.
 template <int SPLIT>

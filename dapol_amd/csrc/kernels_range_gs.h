@@ -51,9 +51,9 @@ __device__ __forceinline__ void write_digits_gs(const RangeArgs& A, size_t p, in
 // of ONE 128-byte line of a proof's vector (the line is fetched once, by one pair of load instructions) and write the four
 // components of ONE 16-byte digit element; then the proofs, so that a wavefront's store is 256 contiguous bytes per window.
 // grid = ceil(cb * 2N / 64) blocks of 64.
-// The producers walk their blocks in a GRID-STRIDE loop (GS_BLOCKS): launched with as many blocks as there are, each does one;
-// launched with fewer (host_range.inc, DAPOL_PRODUCER_WAVES: an experiment that caps how many wavefront slots an HBM-bound
-// producer may hold beside another chunk's VALU-bound sweep), each walks several.
+// The producers walk their blocks in a GRID-STRIDE loop (GS_BLOCKS): launched with as many blocks as there are (what host_range.inc
+// does), each does one; launched with fewer, each walks several (the capped grids of round 4 were slower and are gone:
+// profiles/archive/r07d_producer_waves_ab.txt).
 #define GS_BLOCKS(A, vb) for (size_t vb = blockIdx.x, nb_ = ((size_t)(A).B * (size_t)(2 * (A).N) + 63) / 64; vb < nb_; vb += gridDim.x)
 __device__ __forceinline__ bool gs_thread(const RangeArgs& A, size_t vblock, size_t& p, int& sp) {
     const size_t t = vblock * 64 + threadIdx.x;
