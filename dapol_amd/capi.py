@@ -112,6 +112,9 @@ _SIG = {
     "dapol_entity_proof_size": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "dapol_prove_entities_upper": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
                                                     _P, _P, _P, _P, _P, _P, _P]),
+    "dapol_shared_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),
+    "dapol_prove_entities_shared": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
+                                                     _P, _P, _P, _P, _P, _P, _P, _P]),
     "dapol_workload_create": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_create_shard": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_build": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(WorkloadStats)]),
@@ -459,6 +462,17 @@ def batch_siblings(height, leaf_idx):
     return level, index
 
 
+def shared_plan(height, leaf_idx, policy, aggregation_factor):
+    """dapol_shared_plan (host-only): (distinct subtree keys per sub-proof of the plan, their sum = range proofs that
+    prove_entities_shared computes, b x plan size = what prove_entities computes).  height = siblings per entity."""
+    leaf_idx = _u64(leaf_idx)
+    n_sub = np.zeros(max(height, 0) + 2, np.uint64)              # a plan has at most height + 1 sub-proofs
+    tot, per = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _chk(lib().dapol_shared_plan(height, leaf_idx.shape[0], _ptr(leaf_idx), policy, aggregation_factor, _ptr(n_sub), ctypes.byref(tot), ctypes.byref(per)))
+    b = leaf_idx.shape[0]
+    return n_sub[:per.value // b if b else 0], int(tot.value), int(per.value)
+
+
 COMM_ID_BYTES, RECORD_BYTES = 128, 104
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 
@@ -698,6 +712,22 @@ class Tree:
         else:
             _chk(lib().dapol_prove_entities(self.ctx.h, self.h, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(seed), _ptr(C), _ptr(H), _ptr(out)))
         return C, H, out
+
+    def prove_entities_shared(self, leaf_idx, policy, aggregation_factor, n_bits, nonce_seed, upper=None):
+        """dapol_prove_entities_shared: prove_entities' outputs with every distinct sub-proof statement of the call proven once
+        (strictly increasing leaf_idx; no tape mode).  Returns (path_C, path_H, blobs, range proofs actually computed)."""
+        leaf_idx = _u64(leaf_idx)
+        nu = 0 if upper is None else len(upper[2])
+        b, h = leaf_idx.shape[0], self.height + nu
+        es = lib().dapol_entity_proof_size(h, policy, aggregation_factor, n_bits)
+        C, H = np.zeros((b, h, 32), np.uint8), np.zeros((b, h, self.ctx.hb), np.uint8)
+        out = np.zeros((b, max(es, 1)), np.uint8)
+        seed = _u8(np.frombuffer(nonce_seed, np.uint8))
+        uC, uH, uv, ur = (None,) * 4 if not nu else (_u8(upper[0], nu, 32), _u8(upper[1], nu, 32), _u64(upper[2]), _u8(upper[3], nu, 32))
+        unique = ctypes.c_uint64(0)
+        _chk(lib().dapol_prove_entities_shared(self.ctx.h, self.h, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(seed), nu,
+                                               _ptr(uC), _ptr(uH), _ptr(uv), _ptr(ur), _ptr(C), _ptr(H), _ptr(out), ctypes.byref(unique)))
+        return C, H, out, int(unique.value)
 
 
 class Workload:

@@ -19,6 +19,7 @@
 #include "kernels_range_gs.h"
 #include "kernels_verify.h"
 #include "kernels_leaf.h"
+#include "kernels_shared.h"
 
 using namespace dapol;
 
@@ -1658,6 +1659,7 @@ int32_t dapol_tree_paths(dapol_tree* tree, size_t b, const uint64_t* leaf_idx, u
 }
 
 #include "host_range.inc"
+#include "host_shared.inc"
 #include "host_leaf.inc"
 #include "host_wire.inc"
 #include "host_batch.inc"

@@ -1,0 +1,181 @@
+// dapol_prove_entities_shared / dapol_shared_plan: every distinct sub-proof statement of a call is proven once and written into the
+// blob of every entity that contains it (the reference's generate_all_proofs DFS, src/dapol/mod.rs:216-314, with
+// generate_proof_by_new_com / remove_proof_by_last_com, src/range/padding.rs:120-166, splitting.rs:131-178: the sub-proof over the
+// upper siblings of a path is computed once for every leaf below that point).
+//
+// A sub-proof {start, count, m} of the plan over H siblings has the KEY DEPTH D = the largest depth below the root among its siblings
+// (sibling i lies at depth i + 1 in root-first order, H - i in leaf-first order; the siblingless pad proof of aggregation 0 has D = 0),
+// and an entity's SUBTREE KEY for it is S = its leaf index with the low H - D bits cleared: all siblings of the sub-proof are functions
+// of S alone.  The proof's bytes are those of dapol_range_prove_batch over these parties with stream id S and slot base 0.
+
+// shift[s] = H - D of sub-proof s under the call's sibling order (64: the key is 0 -- never used as a shift count)
+static void shared_shifts(const std::vector<SubProof>& plan, int H, bool leaf_first, uint8_t* shift) {
+    for (size_t s = 0; s < plan.size(); s++) {
+        const int D = plan[s].count == 0 ? 0 : leaf_first ? H - plan[s].start : plan[s].start + plan[s].count;
+        shift[s] = (uint8_t)(H - D);
+    }
+}
+static inline uint64_t shared_key_host(uint64_t idx, unsigned shift) { return shift >= 64 ? 0ull : (idx >> shift) << shift; }
+static bool strictly_increasing(size_t b, const uint64_t* idx) {
+    for (size_t i = 1; i < b; i++) if (idx[i] <= idx[i - 1]) return false;
+    return true;
+}
+
+int32_t dapol_shared_plan(int32_t height, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor, uint64_t* n_unique_out,
+                          uint64_t* total_unique, uint64_t* total_per_entity) {
+    WIRE_SCOPE();
+    if (b && !leaf_idx) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    if (height < 0 || height > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
+    std::vector<SubProof> plan;
+    if (!policy_plan(policy, height, aggregation_factor, plan)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation_factor");
+    if (!strictly_increasing(b, leaf_idx) || (b && height < 64 && (leaf_idx[b - 1] >> height) != 0))
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "leaf indexes must be strictly increasing and below 2^height");
+    std::vector<uint8_t> shift(plan.size());
+    shared_shifts(plan, height, g_wire.siblings_leaf_first != 0, shift.data());
+    uint64_t tot = 0;
+    for (size_t s = 0; s < plan.size(); s++) {
+        uint64_t u = b ? 1 : 0;
+        for (size_t e = 1; e < b; e++) u += shared_key_host(leaf_idx[e], shift[s]) != shared_key_host(leaf_idx[e - 1], shift[s]);
+        if (n_unique_out) n_unique_out[s] = u;
+        tot += u;
+    }
+    if (total_unique) *total_unique = tot;
+    if (total_per_entity) *total_per_entity = (uint64_t)b * (uint64_t)plan.size();
+    return DAPOL_OK;
+}
+
+static int32_t inclusive_scan_u32(hipStream_t st, const uint32_t* in, uint32_t* out, size_t n) {
+    size_t tmp = 0;
+    HIPCHK(rocprim::inclusive_scan(nullptr, tmp, in, out, n, rocprim::plus<uint32_t>(), st));
+    DevBuf<uint8_t> d;
+    HIPCHK(d.alloc(tmp ? tmp : 1));
+    HIPCHK(rocprim::inclusive_scan(d.p, tmp, in, out, n, rocprim::plus<uint32_t>(), st));
+    HIPCHK(hipStreamSynchronize(st));                        // (the temporary storage goes at return)
+    return DAPOL_OK;
+}
+
+// The shared counterpart of prove_policy_device: pv / pr / pC are the gathered [b][H] siblings, d_idx the b ascending leaf indexes.
+static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t b, int H, const uint64_t* pv, const uint32_t* pr,
+                                          const uint32_t* pC, int n_bits, const uint32_t* d_seed, const uint64_t* d_idx, uint32_t* d_range,
+                                          uint64_t* unique_out) {
+    hipStream_t st = ctx->stream;
+    if (plan.size() > SHARED_MAX_SUB || (uint64_t)b * (plan.size() + 1) >= (1ull << 32))
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "too many sub-proofs in one call (entities x plan size must stay below 2^32)");
+    SharedPlanDev P{};
+    P.n_sub = (uint32_t)plan.size(); P.H = (uint32_t)H;
+    shared_shifts(plan, H, g_wire.siblings_leaf_first != 0, P.shift);
+    uint32_t q = 0;
+    for (size_t s = 0; s < plan.size(); s++) {
+        P.start[s] = (uint8_t)plan[s].start; P.count[s] = (uint8_t)plan[s].count;
+        const uint32_t pieces = (uint32_t)(dapol_range_proof_size(n_bits, plan[s].m) / 16);
+        if (P.n_groups && P.g[P.n_groups - 1].m == (uint32_t)plan[s].m) P.g[P.n_groups - 1].k++;
+        else {
+            if (P.n_groups == SHARED_MAX_GROUPS) return fail(DAPOL_ERR_INVALID_ARGUMENT, "the plan has too many runs of equal-sized sub-proofs");
+            SharedGroup& G = P.g[P.n_groups++];
+            G.s0 = (uint32_t)s; G.k = 1; G.m = (uint32_t)plan[s].m; G.pieces = pieces; G.q0 = q;
+        }
+        q += pieces;
+    }
+    P.entity_pieces = q;
+    // heads and ranks: rank[s][e] = heads up to and including (s, e) in plan order, so rank - 1 is the compact row of the statement
+    // that (s, e) belongs to -- its own if it is a head, its predecessors' otherwise; the last element (a closing zero flag) counts
+    // all heads.  Row 0 of every sub-proof is a head: a group's first compact row is rank[s0][0] - 1.
+    const size_t nf = (size_t)P.n_sub * b + 1;
+    DevBuf<uint32_t> flag, rank;
+    HIPCHK(flag.alloc(nf)); HIPCHK(rank.alloc(nf));
+    hipLaunchKernelGGL(k_shared_heads, dim3(nblk(nf, 256)), dim3(256), 0, st, P, b, d_idx, flag.p);
+    LAUNCH_CHECK();
+    int32_t rc = inclusive_scan_u32(st, flag.p, rank.p, nf);
+    if (rc) return rc;
+    std::vector<uint32_t> g_first(P.n_groups + 1);           // compact row at which each group starts; the last one: all of them
+    for (uint32_t gi = 0; gi <= P.n_groups; gi++) {
+        const size_t at = gi < P.n_groups ? (size_t)P.g[gi].s0 * b : nf - 1;
+        HIPCHK(hipMemcpyAsync(&g_first[gi], rank.p + at, 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t gi = 0; gi < P.n_groups; gi++) g_first[gi]--;
+    if (unique_out) *unique_out = g_first[P.n_groups];
+    // compact gather: the head rows' parties, group after group
+    size_t parties = 0, words = 0;
+    std::vector<size_t> p_off(P.n_groups);
+    for (uint32_t gi = 0; gi < P.n_groups; gi++) {
+        const size_t U = g_first[gi + 1] - g_first[gi];
+        p_off[gi] = parties; P.g[gi].word_off = words;
+        parties += U * P.g[gi].m; words += U * (size_t)P.g[gi].pieces * 4;
+    }
+    DevBuf<uint64_t> vals, stream;
+    DevBuf<uint32_t> blind, Vc, proofs;
+    HIPCHK(vals.alloc(parties)); HIPCHK(blind.alloc(parties * 8)); HIPCHK(Vc.alloc(parties * 8)); HIPCHK(stream.alloc(g_first[P.n_groups]));
+    HIPCHK(proofs.alloc(words));
+    const uint32_t* Bb_comp = ctx->gens_comp.p + (size_t)ctx->tv.row_Bb(0) * 8;
+    for (uint32_t gi = 0; gi < P.n_groups; gi++) {
+        const SharedGroup& G = P.g[gi];
+        hipLaunchKernelGGL(k_shared_gather, dim3(nblk(b * (size_t)G.k * (size_t)G.m, 256)), dim3(256), 0, st, P, gi, b, d_idx, flag.p, rank.p, pv, pr, pC,
+                           Bb_comp, vals.p + p_off[gi], blind.p + p_off[gi] * 8, Vc.p + p_off[gi] * 8, stream.p + g_first[gi]);
+        LAUNCH_CHECK();
+    }
+    // one call of the range prover per group: a stream id per row, slot base 0.  One after the other, as prove_policy_device's
+    // sequential branch: each call returns after its kernels have drained, so an error return frees nothing that is still in use.
+    for (uint32_t gi = 0; gi < P.n_groups; gi++) {
+        const SharedGroup& G = P.g[gi];
+        rc = range_prove_device(ctx, n_bits, (int)G.m, g_first[gi + 1] - g_first[gi], vals.p + p_off[gi], blind.p + p_off[gi] * 8, Vc.p + p_off[gi] * 8, d_seed,
+                                stream.p + g_first[gi], 0, nullptr, proofs.p + G.word_off, nullptr);
+        if (rc) return rc;
+    }
+    // scatter: every (entity, sub-proof) copies its proof from its compact row
+    hipLaunchKernelGGL(k_shared_scatter, dim3(nblk(b * (size_t)P.entity_pieces, 256)), dim3(256), 0, st, P, b, rank.p, (const uint4*)proofs.p, (uint4*)d_range);
+    LAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(st));
+    return DAPOL_OK;
+}
+
+int32_t dapol_prove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor,
+                                    int32_t n_bits, const uint8_t nonce_seed32[32], int32_t n_upper, const uint8_t* up_C32, const uint8_t* up_H32,
+                                    const uint64_t* up_v, const uint8_t* up_r32, uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out,
+                                    uint64_t* unique_subproofs_out) {
+    WIRE_SCOPE();
+    if (!ctx || !tree || tree->ctx != ctx || !nonce_seed32 || (b && (!leaf_idx || !range_out)) || n_upper < 0 || n_upper > 16)
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "null or out-of-range argument");
+    if (n_upper) NEEDS_32_BYTE_DIGEST(ctx, "the sharded (multi-GPU) path");
+    const int H = tree->height + n_upper;
+    if (H > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
+    const size_t es = dapol_entity_proof_size(H, policy, aggregation_factor, n_bits);
+    if (es == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation_factor / n_bits");
+    std::vector<SubProof> plan;
+    policy_plan(policy, H, aggregation_factor, plan);
+    for (auto& s : plan)
+        if (s.m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
+    if (!strictly_increasing(b, leaf_idx)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "leaf indexes must be strictly increasing");
+    if (b == 0) {
+        if (unique_subproofs_out) *unique_subproofs_out = 0;
+        return DAPOL_OK;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t tot = b * (size_t)H;
+    DevBuf<uint64_t> dl, pv;
+    DevBuf<uint32_t> dseed, dC, dH, dout, pr, pos;
+    UpperDev up;
+    HIPCHK(dl.alloc(b)); HIPCHK(dseed.alloc(8)); HIPCHK(dC.alloc(tot * 8)); HIPCHK(dH.alloc(tot * (size_t)ctx_hw(ctx))); HIPCHK(dout.alloc(b * es / 4));
+    HIPCHK(pv.alloc(tot)); HIPCHK(pr.alloc(tot * 8)); HIPCHK(pos.alloc(b));
+    HIPCHK(hipMemcpyAsync(dl.p, leaf_idx, b * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dseed.p, nonce_seed32, 32, hipMemcpyHostToDevice, st));
+    int32_t rc = up.upload(st, n_upper, up_C32, up_H32, up_v, up_r32);
+    if (rc) return rc;
+    PathOut po{dC.p, dH.p, pv.p, pr.p};
+    rc = tree_paths_device(tree, b, dl.p, po, pos.p, n_upper);
+    if (rc) return rc;
+    if (n_upper) {
+        hipLaunchKernelGGL(k_tree_path_upper, dim3(nblk(b * (size_t)n_upper, 256)), dim3(256), 0, st, b, tree->height, n_upper, g_wire.siblings_leaf_first,
+                           up.view.C, up.view.H, up.view.v, up.view.r, po);
+        LAUNCH_CHECK();
+    }
+    uint64_t unique = 0;
+    rc = prove_policy_shared_device(ctx, plan, b, H, pv.p, pr.p, dC.p, n_bits, dseed.p, dl.p, dout.p, &unique);
+    if (rc) return rc;
+    if (path_C32) HIPCHK(hipMemcpy(path_C32, dC.p, tot * 32, hipMemcpyDeviceToHost));
+    if (path_H32) HIPCHK(hipMemcpy(path_H32, dH.p, tot * ctx_hash_bytes(ctx), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(range_out, dout.p, b * es, hipMemcpyDeviceToHost));
+    if (unique_subproofs_out) *unique_subproofs_out = unique;
+    return DAPOL_OK;
+}

@@ -404,12 +404,24 @@ class Dapol {
     }
     // Many single-leaf proofs in one GPU batch (the throughput path).
     std::optional<std::vector<DapolProof>> generate_proofs(const std::vector<uint64_t>& leaves, const Bytes32& nonce_seed, int n_bits = 64) const {
+        return prove_many(leaves, nonce_seed, n_bits, false);
+    }
+    // The same proofs with every distinct sub-proof statement proven once (dapol_prove_entities_shared; the crate's
+    // generate_all_proofs DFS, mod.rs:216-314): strictly increasing leaves, same layout, verified and serialised like
+    // generate_proofs' -- only the nonce streams differ (keyed by the subtree a sub-proof speaks about, not by the leaf).
+    std::optional<std::vector<DapolProof>> generate_proofs_shared(const std::vector<uint64_t>& leaves, const Bytes32& nonce_seed, int n_bits = 64) const {
+        return prove_many(leaves, nonce_seed, n_bits, true);
+    }
+  private:
+    std::optional<std::vector<DapolProof>> prove_many(const std::vector<uint64_t>& leaves, const Bytes32& nonce_seed, int n_bits, bool shared) const {
         size_t es = dapol_entity_proof_size(height_, (int)policy_, (int)aggregation_factor_, n_bits);
         if (es == 0) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
         size_t b = leaves.size(), h = (size_t)height_;
         std::vector<uint8_t> C(b * h * 32), H(b * h * 32), R(b * es);
-        int32_t rc = dapol_prove_entities(ctx_->get(), tree_.get(), b, leaves.data(), (int)policy_, (int)aggregation_factor_, n_bits,
-                                          nonce_seed.data(), C.data(), H.data(), R.data());
+        int32_t rc = shared ? dapol_prove_entities_shared(ctx_->get(), tree_.get(), b, leaves.data(), (int)policy_, (int)aggregation_factor_, n_bits,
+                                                          nonce_seed.data(), 0, nullptr, nullptr, nullptr, nullptr, C.data(), H.data(), R.data(), nullptr)
+                            : dapol_prove_entities(ctx_->get(), tree_.get(), b, leaves.data(), (int)policy_, (int)aggregation_factor_, n_bits,
+                                                   nonce_seed.data(), C.data(), H.data(), R.data());
         if (rc == DAPOL_ERR_UNKNOWN_LEAF) return std::nullopt;
         check(rc);
         std::vector<DapolProof> out(b);
@@ -425,7 +437,6 @@ class Dapol {
         }
         return out;
     }
-  private:
     std::map<LiabilityId, uint64_t> id_to_idx_map_;
     std::shared_ptr<Context> ctx_;
     std::shared_ptr<dapol_tree> tree_;

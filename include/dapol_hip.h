@@ -279,6 +279,44 @@ int32_t dapol_prove_entities_upper(dapol_ctx* ctx, dapol_tree* tree, size_t b, c
                                    const uint8_t* up_C32, const uint8_t* up_H32, const uint64_t* up_v, const uint8_t* up_r32,
                                    uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out);
 
+/* SHARED sub-proofs -- the counterpart of the reference's test-only DFS Dapol::generate_all_proofs (src/dapol/mod.rs:216-314) with
+ * generate_proof_by_new_com / remove_proof_by_last_com (src/range/padding.rs:120-166, splitting.rs:131-178): a sub-proof over the
+ * upper siblings of a path is the same statement for every leaf below that point, so it is proven ONCE per call and written into
+ * the blob of every entity that contains it.  The blobs keep dapol_prove_entities' layout (dapol_entity_proof_size, the order of
+ * the policy's plan, the wire format): dapol_verify_entities, dapol_range_proofs_serialize and dapol_proof_serialize take them as
+ * they are.  Sharing leaks nothing: the shared object is a range proof over sibling commitments that each of its recipients holds
+ * in its Merkle path already.
+ *   Definition.  H = tree height + n_upper siblings per entity, in dapol_tree_paths' order (dapol_wire_config.siblings_leaf_first):
+ * sibling i lies at depth i + 1 below the root (root side first, the default) or H - i (leaf first).  The KEY DEPTH D of a
+ * sub-proof {start, count, m} of the plan is the largest depth among its siblings (start + count, or H - start leaf first; 0 for
+ * the siblingless pad proof of aggregation_factor = 0).  The SUBTREE KEY S of an entity for it is its global leaf index with the low
+ * H - D bits cleared.  The sub-proof's bytes are those of dapol_range_prove_batch(ctx, n_bits, m, 1, v, r, nonce_seed, &S, 0, NULL,
+ * out) over its siblings in order, padded to m parties with (0, Scalar::one()).  The only difference from dapol_prove_entities is
+ * the nonce stream: id S and slot base 0 instead of the leaf index and a slot base that runs through the plan; the key stays bound
+ * to the statement (top of this header), so equal inputs give equal bytes and another statement another key.  Where the plan's
+ * only sub-proof has D = H (padding with aggregation_factor = H, root side first) the blobs equal dapol_prove_entities' byte for byte.
+ *   dapol_shared_plan: host-only index arithmetic (no GPU, no tree).  For strictly increasing leaf_idx below 2^height (else
+ * DAPOL_ERR_INVALID_ARGUMENT) n_unique_out[s] (may be NULL) = distinct keys of sub-proof s of the plan among the b leaves,
+ * *total_unique their sum = range proofs the shared call computes, *total_per_entity = b x plan size = what dapol_prove_entities
+ * computes.  `height` is H.  Honours the sibling order of dapol_wire_config.
+ *   dapol_prove_entities_shared: arguments and outputs as dapol_prove_entities_upper (n_upper = 0: a plain tree; 64-byte digests
+ * with n_upper = 0 only).  leaf_idx must be strictly increasing (DAPOL_ERR_INVALID_ARGUMENT otherwise): the keys of every depth
+ * then ascend and equal keys are adjacent.  *unique_subproofs_out (may be NULL) = range proofs actually computed.  Refusals as
+ * dapol_prove_entities; an unknown leaf -> DAPOL_ERR_UNKNOWN_LEAF with no output written; b = 0 is DAPOL_OK.  Entities x plan
+ * size must stay below 2^32 per call.  There is NO tape mode: a tape is one RNG per entity by construction, which is exactly what
+ * sharing gives up.
+ *   When to use it (tools/bench_shared.py): the time follows the sum of m over the distinct statements.
+ * 2^20 random leaves at height 32, 64-bit proofs, one MI355X, whole call with the blobs copied back: padding / 16 20.0 -> 9.3 s (x2.15;
+ * the sum-of-m ratio is 2.29), splitting / 24 19.7 -> 10.7 s (x1.85 of 1.91); padding / 32, where dapol_shared_plan reports nothing
+ * to share and the bytes are dapol_prove_entities', 18.671 -> 18.675 s: heads + scan + scatter cost +0.02 %, below the 0.1 %
+ * run-to-run spread, so either call serves there. */
+int32_t dapol_shared_plan(int32_t height, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor,
+                          uint64_t* n_unique_out, uint64_t* total_unique, uint64_t* total_per_entity);
+int32_t dapol_prove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b, const uint64_t* leaf_idx, int32_t policy,
+                                    int32_t aggregation_factor, int32_t n_bits, const uint8_t nonce_seed32[32], int32_t n_upper,
+                                    const uint8_t* up_C32, const uint8_t* up_H32, const uint64_t* up_v, const uint8_t* up_r32,
+                                    uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out, uint64_t* unique_subproofs_out);
+
 /* Serializable for RangeProofPadding / RangeProofSplitting (src/range/padding.rs:38-69, src/range/splitting.rs:36-84):
  * the range-proof blob of ONE entity as written by dapol_prove_entities <-> R::serialize() bytes
  * ((aggregated_num ||) (size || proof)... || individual_num || proofs...; field widths src/range/mod.rs:18-21).
