@@ -85,7 +85,7 @@ static int32_t comm_wait(dapol_comm* c, hipStream_t st, const char* what, int li
     for (unsigned spins = 0;; spins++) {
         hipError_t e = hipEventQuery(c->ev);
         if (e == hipSuccess) return DAPOL_OK;
-        if (e != hipErrorNotReady) return fail_hip(e, what, line);
+        if (e != hipErrorNotReady) return fail_hip(e, what, "host_comm.inc", line);
         (void)hipGetLastError();
         const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
         if ((spins & 63) == 63 || ms > 5) {

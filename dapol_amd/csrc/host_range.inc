@@ -353,7 +353,7 @@ static int32_t range_prove_device(dapol_ctx* ctx, int n, int m, size_t B, const 
             break;
         }
         (void)hipGetLastError();
-        if (e != hipErrorOutOfMemory || (P.nlanes == 1 && P.chunk <= 64)) return fail_hip(e, "scratch allocation", __LINE__);
+        if (e != hipErrorOutOfMemory || (P.nlanes == 1 && P.chunk <= 64)) return fail_hip(e, "scratch allocation", __FILE__, __LINE__);
         if (P.nlanes > 1) P.nlanes--;
         else P.chunk = (P.chunk + 1) / 2;
     }

@@ -361,6 +361,27 @@ __global__ __launch_bounds__(256) void k_tree_pad_level(TableView tbl, LevelView
     st_p3(extpad + q * 40, pB);
 }
 
+// Paddable::padding (src/dapol/node.rs:86-88): new(0, random blinding) with the draw keyed by the node's position.
+__global__ void k_padding_nodes(TableView tbl, size_t n, const uint32_t* pad_seed, const uint8_t* level, const uint64_t* index, uint32_t* C,
+                                uint32_t* H, uint32_t* r) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t seed[8], wide[16], rB[8], cB[8], hB[8];
+    for (int k = 0; k < 8; k++) seed[k] = pad_seed[k];
+    seed_wide(wide, seed, 1u, (uint64_t)level[i], index[i]);
+    sc rm;
+    sc_from_wide(rm, wide);
+    sc_from_mont(rB, rm);
+    ge_p3 p;
+    ge_identity(p);
+    tbl_fixed_mul_add(p, tbl, tbl.row_Bb(0), rB);
+    ge_compress(cB, p);
+    node_hash32(tbl.digest, hB, cB);
+    st8(C + i * 8, cB);
+    st8(H + i * 8, hB);
+    st8(r + i * 8, rB);
+}
+
 // ------------------------------------------------------------------------------------- incremental update
 // smtree's `update` (src/dapol/mod.rs:210-213 -> SparseMerkleTree::update) re-merges ONE root-to-leaf path.  Replacing the
 // liabilities of k leaves that already exist changes no structure: the same nodes, parents and padding siblings (those are keyed
@@ -1085,6 +1106,37 @@ __global__ __launch_bounds__(64) void k_wide_path_walk(size_t b, const uint32_t*
         else ld16(h, wv.H + ((lv.idx[p] & 1ull) ? (size_t)p - 1 : (size_t)p + 1) * 16);
         st16(outH16 + slot * 16, h);
         p = lv.parent[p];
+    }
+}
+
+// Mergeable::merge on compressed records
+template <int HW>
+__device__ __forceinline__ void ldh(uint32_t* w, const uint32_t* p) { ld8(w, p); if (HW == 16) ld8(w + 8, p + 8); }
+template <int HW>
+__device__ __forceinline__ void sth(uint32_t* p, const uint32_t* w) { st8(p, w); if (HW == 16) st8(p + 8, w + 8); }
+template <int HW>
+__global__ void k_merge_records(int dg, size_t n, const uint32_t* CL, const uint32_t* HL, const uint64_t* vL, const uint32_t* rL,
+                                const uint32_t* CR, const uint32_t* HR, const uint64_t* vR, const uint32_t* rR, uint32_t* C, uint32_t* H,
+                                uint64_t* v, uint32_t* r, uint32_t* bad) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t cl[8], cr[8], hl[HW], hr[HW], cp[8], hp[HW];
+    ld8(cl, CL + i * 8); ld8(cr, CR + i * 8); ldh<HW>(hl, HL + i * HW); ldh<HW>(hr, HR + i * HW);
+    ge_p3 a, b, p;
+    bool ok = ge_decompress(a, cl) & ge_decompress(b, cr);
+    if (!ok) { atomicOr(bad, 1u); return; }
+    ge_add(p, a, b);
+    ge_compress(cp, p);
+    node_hash_parent_w<HW>(dg, hp, cl, cr, hl, hr);
+    st8(C + i * 8, cp);
+    sth<HW>(H + i * HW, hp);
+    if (v) {
+        uint32_t ra[8], rb[8], rp[8];
+        ld8(ra, rL + i * 8); ld8(rb, rR + i * 8);
+        sc ma, mb, ms;
+        sc_to_mont(ma, ra); sc_to_mont(mb, rb); sc_add(ms, ma, mb); sc_from_mont(rp, ms);
+        st8(r + i * 8, rp);
+        v[i] = vL[i] + vR[i];
     }
 }
 
