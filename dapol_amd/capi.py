@@ -103,6 +103,8 @@ _SIG = {
                                                ctypes.c_int32, _P, _P, _P]),
     "dapol_verify_entities_checked": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, ctypes.c_int32,
                                                        ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P]),
+    "dapol_verify_entities_shared": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, ctypes.c_int32,
+                                                      ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P]),
     "dapol_verify_batch_checked": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, ctypes.c_int32,
                                                     ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P]),
     "dapol_batch_siblings": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, _P]),
@@ -414,6 +416,24 @@ class Context:
         _chk(lib().dapol_verify_entities_checked(self.h, height, b, _ptr(leaf_idx), _ptr(lC), _ptr(lH), pC.shape[0], _ptr(pC), _ptr(pH), _ptr(rC), _ptr(rH),
                                                  policy, aggregation_factor, n_bits, _ptr(rp), rp.shape[0], _ptr(seed), _ptr(ok)))
         return ok
+
+    def verify_entities_shared(self, height, leaf_idx, leaf_C, leaf_H, path_C, path_H, root_C, root_H, policy, aggregation_factor, n_bits, range_proofs,
+                               verify_seed=None):
+        """dapol_verify_entities_shared: verify_entities' verdicts with every run of equal sub-proofs (equal proof bytes over equal
+        sibling commitments) checked once.  Returns (ok, unique): unique = range proofs actually checked."""
+        leaf_idx = _u64(leaf_idx)
+        b = leaf_idx.shape[0]
+        lC, lH = _u8(leaf_C, b, 32), _u8(leaf_H, b, self.hb)
+        pC, pH = _u8(path_C).reshape(-1, 32), _u8(path_H).reshape(-1, self.hb)
+        rp = _u8(range_proofs).reshape(-1)
+        rC, rH = _u8(np.frombuffer(root_C, np.uint8)), _u8(np.frombuffer(root_H, np.uint8))
+        seed = _u8(np.frombuffer(verify_seed, np.uint8)) if verify_seed is not None else None   # None: the library draws one from the OS
+        ok, unique = np.zeros(b, np.uint8), ctypes.c_uint64(0)
+        if pH.shape[0] != pC.shape[0]:
+            return ok, 0
+        _chk(lib().dapol_verify_entities_shared(self.h, height, b, _ptr(leaf_idx), _ptr(lC), _ptr(lH), pC.shape[0], _ptr(pC), _ptr(pH), _ptr(rC), _ptr(rH),
+                                                policy, aggregation_factor, n_bits, _ptr(rp), rp.shape[0], _ptr(seed), _ptr(ok), ctypes.byref(unique)))
+        return ok, int(unique.value)
 
     def verify_batch(self, height, leaf_idx, leaf_C, leaf_H, sib_C, sib_H, root_C, root_H, policy, aggregation_factor, n_bits, range_proofs,
                      verify_seed=None):

@@ -19,6 +19,7 @@
 #include "kernels_verify.h"
 #include "kernels_leaf.h"
 #include "kernels_shared.h"
+#include "kernels_verify_shared.h"
 
 using namespace dapol;
 
@@ -60,7 +61,7 @@ static const char* knob(const char* name) {
     return on ? getenv(name) : nullptr;
 }
 // Fault injection and limit overrides that exist for tests/ only (DAPOL_TEST_FAIL_AFTER_FORK, DAPOL_TEST_FAIL_UPDATE_MIDWAY / _REMOVE_MIDWAY,
-// DAPOL_LEAF_MAX_TRIES: they make healthy calls fail, or change when DapolError::FailedToMapIndex fires) need a SECOND opt-in,
+// DAPOL_LEAF_MAX_TRIES, DAPOL_VSHARED_FORWARD_MAX: they make healthy calls fail, or change when DapolError::FailedToMapIndex fires) need a SECOND opt-in,
 // DAPOL_TEST_HOOKS=1, read once per process: the measurement scripts of tools/ export DAPOL_ENV_KNOBS alone and can never trip them,
 // and a call site costs a flag test instead of a getenv + strcmp (round-4 advisor).
 static const char* test_knob(const char* name) {
@@ -446,6 +447,7 @@ int32_t dapol_commit_hash_batch(dapol_ctx* ctx, size_t n, const uint64_t* v, con
 #include "host_tree_edit.inc"
 #include "host_range.inc"
 #include "host_shared.inc"
+#include "host_verify_shared.inc"
 #include "host_leaf.inc"
 #include "host_wire.inc"
 #include "host_batch.inc"

@@ -563,37 +563,30 @@ static int32_t verify_policy_device(dapol_ctx* ctx, const std::vector<SubProof>&
     return DAPOL_OK;
 }
 
-// DapolProof::verify (src/proof/mod.rs:41-47, :89-95) for b single-leaf proofs: Merkle re-merge, then R::verify over the
-// sibling commitments (src/range/padding.rs:169-196, src/range/splitting.rs:181-210).
-int32_t dapol_verify_entities(dapol_ctx* ctx, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* leaf_C32,
-                              const uint8_t* leaf_H32, const uint8_t* path_C32, const uint8_t* path_H32, const uint8_t root_C32[32],
-                              const uint8_t root_H32[32], int32_t policy, int32_t aggregation_factor, int32_t n_bits,
-                              const uint8_t* range_proofs, const uint8_t verify_seed32[32], uint8_t* ok) {
-    WIRE_SCOPE();
-    if (!ctx || !root_C32 || !root_H32 || (b && (!leaf_idx || !leaf_C32 || !leaf_H32 || !path_C32 || !path_H32 || !range_proofs || !ok)))
-        return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    VERIFY_SEED_OR_OS(verify_seed32)
-    if (height < 0 || height > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
-    std::vector<SubProof> plan;
-    if (!policy_plan(policy, height, aggregation_factor, plan)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation_factor");
-    size_t es = dapol_entity_proof_size(height, policy, aggregation_factor, n_bits);
-    if (es == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad n_bits");
-    if (b == 0) return DAPOL_OK;
-    HIPCHK(hipSetDevice(ctx->device));
+// The device side that dapol_verify_entities and dapol_verify_entities_shared (host_verify_shared.inc) have in common: one arena for the
+// call's inputs and verdict bytes, its upload, the Merkle re-merge queued (on a side stream for a call of few proofs: fg is the
+// caller's guard, and D.side_paths says that the caller has to join ctx->ev_join[2]) and dok set to ones.  v_parties: commitments per
+// entity of the [b][m] scratch dV (0: none).
+struct VerifyCallDev {
+    DevBuf<uint8_t> arena;
+    uint32_t *dPC = nullptr, *dR = nullptr, *dseed = nullptr, *dV = nullptr;
+    uint8_t *dok = nullptr, *dsub = nullptr, *dpath = nullptr;
+    bool side_paths = false;
+};
+static int32_t verify_upload_and_paths(dapol_ctx* ctx, ForkGuard& fg, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* leaf_C32,
+                                       const uint8_t* leaf_H32, const uint8_t* path_C32, const uint8_t* path_H32, const uint8_t root_C32[32],
+                                       const uint8_t root_H32[32], size_t es, const uint8_t* range_proofs, const uint8_t verify_seed32[32],
+                                       size_t v_parties, VerifyCallDev& D) {
     hipStream_t st = ctx->stream;
     const size_t tot = b * (size_t)height;
-    int max_m = 1;
-    for (auto& s : plan) if (s.m > max_m) max_m = s.m;
-    if (max_m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
     // One device arena for the call's inputs and verdict bytes; small calls also stage the nine host arrays into ONE upload
     // (a pageable-memory copy costs ~20 us of latency however small: 0.24 ms of a 2.2 ms single-proof check).
     const size_t hb = ctx_hash_bytes(ctx);                        // leaf_H32 / path_H32 / root_H32: hb bytes per node (32, or 64 for Blake2b)
-    const size_t sizes[12] = {b * 8, b * 32, b * hb, tot * 32 + 32, tot * hb + 64, b * es, 32 + 64, 32, b, b, b, b * (size_t)max_m * 32};
+    const size_t sizes[12] = {b * 8, b * 32, b * hb, tot * 32 + 32, tot * hb + 64, b * es, 32 + 64, 32, b, b, b, b * v_parties * 32};
     size_t offs[12], total = 0;
     for (int i = 0; i < 12; i++) { offs[i] = total; total += align_up(sizes[i], 256); }
-    DevBuf<uint8_t> arena;
-    HIPCHK(arena.alloc(total));
-    uint8_t* base = arena.p;
+    HIPCHK(D.arena.alloc(total));
+    uint8_t* base = D.arena.p;
     uint64_t* dl = (uint64_t*)(base + offs[0]);
     uint32_t *dLC = (uint32_t*)(base + offs[1]), *dLH = (uint32_t*)(base + offs[2]), *dPC = (uint32_t*)(base + offs[3]), *dPH = (uint32_t*)(base + offs[4]);
     uint32_t *dR = (uint32_t*)(base + offs[5]), *droot = (uint32_t*)(base + offs[6]), *dseed = (uint32_t*)(base + offs[7]);
@@ -621,7 +614,6 @@ int32_t dapol_verify_entities(dapol_ctx* ctx, int32_t height, size_t b, const ui
     const bool few = b <= 16384 && !knob("DAPOL_PATHS_LANE");
     const bool side_paths = few && b <= 64 && !knob("DAPOL_VERIFY_ONE_STREAM");
     hipStream_t sp = side_paths ? ctx->side[2] : st;
-    ForkGuard fg(ctx);
     if (side_paths) {
         HIPCHK(hipEventRecord(ctx->ev_fork, st));
         HIPCHK(hipStreamWaitEvent(sp, ctx->ev_fork, 0));
@@ -640,11 +632,43 @@ int32_t dapol_verify_entities(dapol_ctx* ctx, int32_t height, size_t b, const ui
     LAUNCH_CHECK();
     if (side_paths) { HIPCHK(hipEventRecord(ctx->ev_join[2], sp)); FAULT_AFTER_FORK("verify_paths"); }
     HIPCHK(hipMemsetAsync(dok, 1, b, st));
-    int32_t rc = verify_policy_device(ctx, plan, b, height, dPC, dR, es / 4, n_bits, dseed, dok, dsub, dV);
+    D.dPC = dPC; D.dR = dR; D.dseed = dseed; D.dV = dV;
+    D.dok = dok; D.dsub = dsub; D.dpath = dpath;
+    D.side_paths = side_paths;
+    return DAPOL_OK;
+}
+
+// DapolProof::verify (src/proof/mod.rs:41-47, :89-95) for b single-leaf proofs: Merkle re-merge, then R::verify over the
+// sibling commitments (src/range/padding.rs:169-196, src/range/splitting.rs:181-210).
+int32_t dapol_verify_entities(dapol_ctx* ctx, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* leaf_C32,
+                              const uint8_t* leaf_H32, const uint8_t* path_C32, const uint8_t* path_H32, const uint8_t root_C32[32],
+                              const uint8_t root_H32[32], int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                              const uint8_t* range_proofs, const uint8_t verify_seed32[32], uint8_t* ok) {
+    WIRE_SCOPE();
+    if (!ctx || !root_C32 || !root_H32 || (b && (!leaf_idx || !leaf_C32 || !leaf_H32 || !path_C32 || !path_H32 || !range_proofs || !ok)))
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    VERIFY_SEED_OR_OS(verify_seed32)
+    if (height < 0 || height > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
+    std::vector<SubProof> plan;
+    if (!policy_plan(policy, height, aggregation_factor, plan)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation_factor");
+    size_t es = dapol_entity_proof_size(height, policy, aggregation_factor, n_bits);
+    if (es == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad n_bits");
+    if (b == 0) return DAPOL_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int max_m = 1;
+    for (auto& s : plan) if (s.m > max_m) max_m = s.m;
+    if (max_m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
+    VerifyCallDev D;
+    ForkGuard fg(ctx);
+    int32_t rc = verify_upload_and_paths(ctx, fg, height, b, leaf_idx, leaf_C32, leaf_H32, path_C32, path_H32, root_C32, root_H32, es, range_proofs,
+                                         verify_seed32, (size_t)max_m, D);
+    if (rc) return rc;
+    rc = verify_policy_device(ctx, plan, b, height, D.dPC, D.dR, es / 4, n_bits, D.dseed, D.dok, D.dsub, D.dV);
     if (rc) return rc;                                            // (the guard waits for the path kernel)
-    if (side_paths) { HIPCHK(hipStreamWaitEvent(st, ctx->ev_join[2], 0)); fg.joined(2); }
-    hipLaunchKernelGGL(k_and_bytes, dim3(nblk(b, 256)), dim3(256), 0, st, b, dok, dpath);
+    if (D.side_paths) { HIPCHK(hipStreamWaitEvent(st, ctx->ev_join[2], 0)); fg.joined(2); }
+    hipLaunchKernelGGL(k_and_bytes, dim3(nblk(b, 256)), dim3(256), 0, st, b, D.dok, D.dpath);
     LAUNCH_CHECK();
-    HIPCHK(hipMemcpy(ok, dok, b, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ok, D.dok, b, hipMemcpyDeviceToHost));
     return DAPOL_OK;
 }

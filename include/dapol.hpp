@@ -412,7 +412,49 @@ class Dapol {
     std::optional<std::vector<DapolProof>> generate_proofs_shared(const std::vector<uint64_t>& leaves, const Bytes32& nonce_seed, int n_bits = 64) const {
         return prove_many(leaves, nonce_seed, n_bits, true);
     }
+    // Verifies many single-leaf proofs in one call with every run of equal sub-proofs checked once (dapol_verify_entities_shared):
+    // a verdict per proof -- the ones DapolProof::verify gives one by one -- and the number of range proofs actually checked.  Proofs
+    // of generate_proofs_shared in their order share the most; any proofs of one (height, policy, aggregation factor, n_bits) may
+    // be passed.  proofs[i] is checked against leaves[i].
+    static std::pair<std::vector<bool>, uint64_t> verify_proofs_shared(const Context& ctx, const DapolProofNode& root, const std::vector<DapolProofNode>& leaves,
+                                                                       const std::vector<DapolProof>& proofs) {
+        return verify_many_shared(ctx, root, leaves, proofs, nullptr);
+    }
+    static std::pair<std::vector<bool>, uint64_t> verify_proofs_shared(const Context& ctx, const DapolProofNode& root, const std::vector<DapolProofNode>& leaves,
+                                                                       const std::vector<DapolProof>& proofs, const Bytes32& verify_seed) {
+        return verify_many_shared(ctx, root, leaves, proofs, verify_seed.data());
+    }
   private:
+    static std::pair<std::vector<bool>, uint64_t> verify_many_shared(const Context& ctx, const DapolProofNode& root, const std::vector<DapolProofNode>& leaves,
+                                                                     const std::vector<DapolProof>& proofs, const uint8_t* verify_seed) {
+        const size_t b = proofs.size();
+        if (leaves.size() != b) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        std::vector<bool> out(b, false);
+        if (b == 0) return {out, 0};
+        const DapolProof& p0 = proofs[0];
+        std::vector<uint64_t> idx(b);
+        std::vector<uint8_t> lC(b * 32), lH(b * 32), C, H, R;
+        for (size_t e = 0; e < b; e++) {
+            const DapolProof& p = proofs[e];
+            if (p.height != p0.height || p.policy != p0.policy || p.aggregation_factor != p0.aggregation_factor || p.n_bits != p0.n_bits)
+                throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+            idx[e] = p.leaf_index;
+            std::memcpy(&lC[e * 32], leaves[e].com.data(), 32);
+            std::memcpy(&lH[e * 32], leaves[e].hash.data(), 32);
+            for (auto& s : p.merkle_siblings) { C.insert(C.end(), s.com.begin(), s.com.end()); H.insert(H.end(), s.hash.begin(), s.hash.end()); }
+            R.insert(R.end(), p.range_proofs.begin(), p.range_proofs.end());
+        }
+        const size_t n_nodes = C.size() / 32, r_len = R.size();
+        C.push_back(0); H.push_back(0); R.push_back(0);                     // never pass a null data pointer
+        std::vector<uint8_t> ok(b, 0);
+        uint64_t unique = 0;
+        // the length-checked entry point: proofs whose sibling counts or range-proof bytes do not add up are simply invalid
+        check(dapol_verify_entities_shared(ctx.get(), p0.height, b, idx.data(), lC.data(), lH.data(), n_nodes, C.data(), H.data(), root.com.data(),
+                                           root.hash.data(), (int)p0.policy, (int)p0.aggregation_factor, p0.n_bits, R.data(), r_len, verify_seed, ok.data(),
+                                           &unique));
+        for (size_t e = 0; e < b; e++) out[e] = ok[e] != 0;
+        return {out, unique};
+    }
     std::optional<std::vector<DapolProof>> prove_many(const std::vector<uint64_t>& leaves, const Bytes32& nonce_seed, int n_bits, bool shared) const {
         size_t es = dapol_entity_proof_size(height_, (int)policy_, (int)aggregation_factor_, n_bits);
         if (es == 0) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);

@@ -419,6 +419,37 @@ int32_t dapol_verify_batch_checked(dapol_ctx* ctx, int32_t height, size_t k, con
                                    int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint8_t* range_proofs, size_t range_proofs_len,
                                    const uint8_t verify_seed32[32], uint8_t* ok);
 
+/* SHARED sub-proofs on the verifier's side -- the counterpart of dapol_prove_entities_shared: a call that checks many entities'
+ * proofs (an exchange before it publishes them, an auditor who checks everyone's) verifies every run of equal sub-proofs once.
+ * Arguments, refusals and error codes as dapol_verify_entities_checked / dapol_verify_entities (shared or per-entity blobs, decoded
+ * wires and 64-byte digests go in unchanged), plus *unique_subproofs_out (may be NULL).
+ *   Definition.  For sub-proof s = {start, count, m} of the policy's plan, row e REPEATS row e - 1 iff (1) the sub-proof's bytes in
+ * the two blobs are equal and (2) the `count` sibling commitments path_C32[e][start .. start + count) equal those of row e - 1.
+ * That is everything the range check of the sub-proof reads (the pad parties are constants; node hashes are not read).  A row
+ * that does not repeat its predecessor is a HEAD; row 0 always is one.  Every head is verified once, a repeating row receives the
+ * verdict of the head of its run.  ok[e] = the Merkle re-merge of entity e (per entity, unchanged) AND the verdicts of its
+ * sub-proofs.  *unique_subproofs_out = the number of heads = range proofs actually checked.
+ *   It works for any input: no keys, no trust in the leaf indexes and no ordering requirement -- adjacent equal bytes are the only
+ * thing that is shared, so unsorted or per-entity blobs only share less and the result is still dapol_verify_entities' verdict
+ * vector.  The verdict vector is the per-proof one, as everywhere in the verifier: the compact batch goes through the same random
+ * linear combination with its eight-way split fallback, so a bad copy never drags a good neighbour down (a copy and its original
+ * get the same verdict because the verdict is a function of the bytes; the combination's soundness error of about 2^-250 is the
+ * one exception).  The verifier's scalars are bound to the compact batch: their digest covers every distinct proof and commitment.
+ *   Errors and limits.  Length mismatches (n_path_nodes, range_proofs_len) -> ok = 0, *unique = 0, DAPOL_OK.  A bad policy /
+ * aggregation_factor / n_bits, or more parties than the context has -> DAPOL_ERR_INVALID_ARGUMENT.  b = 0 is DAPOL_OK with
+ * *unique = 0.  b x (plan size + 1) must stay below 2^32 (DAPOL_ERR_INVALID_ARGUMENT above).  Calls with b x plan size <= 64 --
+ * the latency regime, where there is nothing to gain -- forward to dapol_verify_entities and report *unique = b x plan size (a test-only override,
+ * DAPOL_VSHARED_FORWARD_MAX behind DAPOL_ENV_KNOBS and DAPOL_TEST_HOOKS, moves that limit).
+ *   When to use it (tools/bench_verify_shared.py): the time of a call is its upload (which sharing cannot
+ * shrink), the per-entity Merkle re-merge, and range checks that follow the sum of m over the distinct rows instead of over all rows.
+ * The tool prints all three per shape; its numbers are not measured yet on an MI355X, so no ratio is claimed here: until they are,
+ * treat this entry point as experimental and prefer dapol_verify_entities.  What the shared
+ * call adds where nothing repeats is one pass over the uploaded blobs (compare), a scan and a gather of every row. */
+int32_t dapol_verify_entities_shared(dapol_ctx* ctx, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* leaf_C32, const uint8_t* leaf_H32,
+                                     size_t n_path_nodes, const uint8_t* path_C32, const uint8_t* path_H32, const uint8_t root_C32[32],
+                                     const uint8_t root_H32[32], int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint8_t* range_proofs,
+                                     size_t range_proofs_len, const uint8_t verify_seed32[32], uint8_t* ok, uint64_t* unique_subproofs_out);
+
 /* Multi-GPU: one process per GPU, rank g owning the top-level subtree with index prefix g (dapol_tree_build_shard /
  * dapol_workload_create_shard).  The reference has no communication (single process, single thread); the sharded path has
  * exactly one exchange step and one final reduce, both RCCL calls inside this library (librccl.so, over xGMI):
