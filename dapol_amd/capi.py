@@ -85,6 +85,7 @@ _SIG = {
     "dapol_tree_node_count": (ctypes.c_int32, [_P, _P, _P]),
     "dapol_tree_update": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P]),
     "dapol_tree_remove": (ctypes.c_int32, [_P, ctypes.c_size_t, _P]),
+    "dapol_tree_insert": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P]),
     "dapol_tree_last_update_path": (ctypes.c_int32, [_P, _P]),
     "dapol_diag_fork_guard_waits": (ctypes.c_int32, [_P]),
     "dapol_diag_verify_fallbacks": (ctypes.c_int32, [_P]),
@@ -663,9 +664,15 @@ class Tree:
         leaf_idx = _u64(leaf_idx)
         _chk(lib().dapol_tree_remove(self.h, leaf_idx.shape[0], _ptr(leaf_idx)))
 
+    def insert(self, leaf_idx, v, r32):
+        """dapol_tree_insert: adds NEW leaves, in any order (all or nothing; an index that is a leaf already, or given twice, is an
+        error).  Chains may share nodes: sibling pairs and whole new subtrees go in place too."""
+        leaf_idx, v, r32 = _u64(leaf_idx), _u64(v), _u8(r32)
+        _chk(lib().dapol_tree_insert(self.h, leaf_idx.shape[0], _ptr(leaf_idx), _ptr(v), _ptr(r32)))
+
     def last_update_path(self):
-        """What the last update or removal did: 0 = rebuilt the tree, 1 = replaced in place, 2 = inserted in place, 3 = both,
-        4 = removed in place."""
+        """What the last update, insert or removal did: 0 = rebuilt the tree, 1 = replaced in place, 2 = inserted in place (disjoint
+        chains), 3 = both, 4 = removed in place, 5 = inserted in place by insert()'s general path."""
         p = ctypes.c_int32(-1)
         _chk(lib().dapol_tree_last_update_path(self.h, ctypes.byref(p)))
         return int(p.value)

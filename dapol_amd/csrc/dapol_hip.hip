@@ -60,7 +60,7 @@ static const char* knob(const char* name) {
     }
     return on ? getenv(name) : nullptr;
 }
-// Fault injection and limit overrides that exist for tests/ only (DAPOL_TEST_FAIL_AFTER_FORK, DAPOL_TEST_FAIL_UPDATE_MIDWAY / _REMOVE_MIDWAY,
+// Fault injection and limit overrides that exist for tests/ only (DAPOL_TEST_FAIL_AFTER_FORK, DAPOL_TEST_FAIL_UPDATE_MIDWAY / _REMOVE_MIDWAY / _INSERT_MIDWAY,
 // DAPOL_LEAF_MAX_TRIES, DAPOL_VSHARED_FORWARD_MAX: they make healthy calls fail, or change when DapolError::FailedToMapIndex fires) need a SECOND opt-in,
 // DAPOL_TEST_HOOKS=1, read once per process: the measurement scripts of tools/ export DAPOL_ENV_KNOBS alone and can never trip them,
 // and a call site costs a flag test instead of a getenv + strcmp (round-4 advisor).

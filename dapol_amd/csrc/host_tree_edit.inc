@@ -1,6 +1,7 @@
-// Edits of a built tree (dapol_tree_update, dapol_tree_remove): the launchers of the three in-place paths -- replace, insert, remove
-// (kernels_ctx_tree.h, "incremental update / insert / remove") -- and the rebuild they fall back to.  What the paths decide on the
-// host is tree_edit_plan.inc; here are the scratch, the launches and the tree's state.  Included by dapol_hip.hip after host_tree.inc.
+// Edits of a built tree (dapol_tree_update, dapol_tree_insert, dapol_tree_remove): the launchers of the in-place paths -- replace,
+// insert (disjoint chains / general), remove (kernels_ctx_tree.h, "incremental update / insert / insert, general / remove") -- and the
+// rebuild they fall back to.  What the paths decide on the host is tree_edit_plan.inc; here are the scratch, the launches and the
+// tree's state.  Included by dapol_hip.hip after host_tree.inc.
 
 // Regions of the edit paths' scratch (dapol_tree_owned::upd_scratch) as offsets, taken in order; ensure() once all are taken.
 struct EditScratch {
@@ -147,9 +148,15 @@ static int32_t adopt_levels(dapol_tree_owned* own, const StagedLevels& S, std::v
     return DAPOL_OK;
 }
 
+// What k_tree_ins_plan_all returned for a batch (dapol_tree_insert plans once, whichever insert path then runs).
+struct InsPlanRead {
+    std::vector<uint32_t> m, pos;        // [k], [k][H + 1]
+    uint32_t flag = 0;                   // bit 1: two chains share a new node; bit 2: an index is a leaf already
+};
 // The incremental path for NEW leaves (kernels_ctx_tree.h, "incremental insert"): E sorted, distinct, none of them in the tree.
-// *done = false and nothing written when two new chains share a node (the caller rebuilds).
-static int32_t tree_insert_incremental(dapol_tree_owned* own, const HostLeaves& E, bool* done) {
+// *done = false and nothing written when two new chains share a node (the caller rebuilds).  pre: the batch has been planned already
+// (no chains shared, every index new); its rows hold what I1 would write.
+static int32_t tree_insert_incremental(dapol_tree_owned* own, const HostLeaves& E, bool* done, const InsPlanRead* pre = nullptr) {
     *done = false;
     dapol_ctx* ctx = own->ctx;
     hipStream_t st = ctx->stream;
@@ -166,16 +173,21 @@ static int32_t tree_insert_incremental(dapol_tree_owned* own, const HostLeaves& 
     { int32_t rc_ = upload_edits(own, E, stage); if (rc_) return rc_; }
     HIPCHK(hipMemcpyAsync(d + o_seed, own->pad_seed, 32, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d + o_flag, 0, 8, st));
-    TreeInsPlan P{k, H, (const uint64_t*)(d + o_idx), (uint32_t*)(d + o_m), (uint32_t*)(d + o_ins), (uint32_t*)(d + o_flag)};
-    hipLaunchKernelGGL(k_tree_ins_plan, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, P);
-    LAUNCH_CHECK();
-    std::vector<uint32_t> hm(k), hins(k * S1);
-    uint32_t conflict = 0;
-    HIPCHK(hipMemcpyAsync(hm.data(), d + o_m, k * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hins.data(), d + o_ins, k * S1 * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&conflict, d + o_flag, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (conflict) return DAPOL_OK;                          // chains that share a node (or an index that exists): the rebuild handles it
+    std::vector<uint32_t> hm_own, hins_own;
+    if (pre) HIPCHK(hipMemcpyAsync(d + o_m, pre->m.data(), k * 4, hipMemcpyHostToDevice, st));
+    else {
+        TreeInsPlan P{k, H, (const uint64_t*)(d + o_idx), (uint32_t*)(d + o_m), (uint32_t*)(d + o_ins), (uint32_t*)(d + o_flag)};
+        hipLaunchKernelGGL(k_tree_ins_plan, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, P);
+        LAUNCH_CHECK();
+        hm_own.resize(k); hins_own.resize(k * S1);
+        uint32_t conflict = 0;
+        HIPCHK(hipMemcpyAsync(hm_own.data(), d + o_m, k * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hins_own.data(), d + o_ins, k * S1 * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&conflict, d + o_flag, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (conflict) return DAPOL_OK;                      // chains that share a node (or an index that exists): the rebuild handles it
+    }
+    const std::vector<uint32_t>&hm = pre ? pre->m : hm_own, &hins = pre ? pre->pos : hins_own;
     const InsertPlan plan = plan_insert(k, H, hm.data(), hins.data());
     HIPCHK(hipMemcpyAsync(d + o_new, plan.newpos.data(), k * S1 * 4, hipMemcpyHostToDevice, st));
     if (!plan.lvl_flat.empty()) HIPCHK(hipMemcpyAsync(d + o_lvl, plan.lvl_flat.data(), plan.lvl_flat.size() * 4, hipMemcpyHostToDevice, st));
@@ -200,6 +212,87 @@ static int32_t tree_insert_incremental(dapol_tree_owned* own, const HostLeaves& 
     for (size_t j = 0; j < k; j++) { own->n_real += hm[j]; own->n_pad += (uint64_t)hm[j] - 2; }     // m - 1 new padding nodes, one dropped
     poison.armed = false;
     *done = true;
+    return DAPOL_OK;
+}
+
+// J1 of dapol_tree_insert (kernels_ctx_tree.h, "incremental insert, general"): where the new leaves E (sorted, distinct) would go at
+// every level, which of them exist and whether chains share nodes.  Nothing of the tree is written.
+static int32_t insert_plan_all(dapol_tree_owned* own, const HostLeaves& E, InsPlanRead& R) {
+    hipStream_t st = own->ctx->stream;
+    const size_t k = E.idx.size(), S1 = (size_t)own->height + 1;
+    EditScratch sc;
+    sc.take(k * 8);
+    const size_t o_m = sc.take(k * 4), o_pos = sc.take(k * S1 * 4), o_flag = sc.take(8, 8);
+    HIPCHK(sc.ensure(own));
+    uint8_t* d = own->upd_scratch.p;
+    HIPCHK(hipMemcpyAsync(d, E.idx.data(), k * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d + o_flag, 0, 8, st));
+    TreeInsPlan P{k, own->height, (const uint64_t*)d, (uint32_t*)(d + o_m), (uint32_t*)(d + o_pos), (uint32_t*)(d + o_flag)};
+    hipLaunchKernelGGL(k_tree_ins_plan_all, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, P);
+    LAUNCH_CHECK();
+    R.m.resize(k); R.pos.resize(k * S1);
+    HIPCHK(hipMemcpyAsync(R.m.data(), d + o_m, k * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(R.pos.data(), d + o_pos, k * S1 * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&R.flag, d + o_flag, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return DAPOL_OK;
+}
+// The general in-place path of dapol_tree_insert: E sorted, distinct, all new and in range, R = its plan rows; chains may share
+// nodes.
+static int32_t tree_insert_general(dapol_tree_owned* own, const HostLeaves& E, const InsPlanRead& R) {
+    dapol_ctx* ctx = own->ctx;
+    hipStream_t st = ctx->stream;
+    const int H = own->height;
+    const size_t k = E.idx.size();
+    InsertGeneralPlan plan = plan_insert_general(H, k, E.idx.data(), R.m.data(), R.pos.data());
+    memcpy(plan.flat.data(), own->pad_seed, 32);
+    const size_t n_new = plan.n_pos.size(), n_pad = plan.pad_pos.size(), slots = plan.max_fresh;
+    // leaves | the plan, one upload | extended points: fresh nodes (two halves, by level parity), new padding nodes
+    EditScratch sc;
+    sc.take(k * 48);
+    const size_t o_flat = sc.take(plan.flat.size() * 4, 16), o_node = sc.take(2 * slots * 160, 16), o_pad = sc.take(n_pad * 160, 16);
+    HIPCHK(sc.ensure(own));
+    uint8_t* d = own->upd_scratch.p;
+    std::vector<uint8_t> stage;
+    { int32_t rc_ = upload_edits(own, E, stage); if (rc_) return rc_; }
+    HIPCHK(hipMemcpyAsync(d + o_flat, plan.flat.data(), plan.flat.size() * 4, hipMemcpyHostToDevice, st));
+    const uint32_t* dw = (const uint32_t*)(d + o_flat);
+    std::vector<RelayoutDel> gains((size_t)plan.D);
+    for (int t = 0; t < plan.D; t++)
+        gains[t] = RelayoutDel{dw + plan.gain_off[t], (uint32_t)plan.gain[t].size(), dw + plan.gain_off[t + 1], (uint32_t)plan.gain[t + 1].size()};
+    StagedLevels staged;
+    { int32_t rc_ = relayout_levels(own, gains, false, staged); if (rc_) return rc_; }
+    TreePoison poison{own, true};                            // the tree's own state changes from here on
+    std::vector<LevelView> hv;
+    { int32_t rc_ = adopt_levels(own, staged, hv); if (rc_) return rc_; }
+    if (test_knob("DAPOL_TEST_FAIL_INSERT_MIDWAY")) return fail(DAPOL_ERR_HIP, "injected failure between the relayout and the new nodes (test knob)");
+    int32_t* node_ext = (int32_t*)(d + o_node);
+    TreeInsGeneral G{n_new, k, n_pad, dw + plan.lvl_off, dw + plan.pos_off, dw + plan.parent_off, dw + plan.sib_off, dw + plan.idx_lo_off, dw + plan.idx_hi_off,
+                     dw + plan.leaf_off, dw + plan.pad_lvl_off, dw + plan.pad_pos_off, (const uint64_t*)(d + k * 8), (const uint32_t*)(d + k * 16), dw,
+                     node_ext, (int32_t*)(d + o_pad), (uint32_t)slots};
+    hipLaunchKernelGGL(k_tree_ins_struct, dim3(nblk(n_new, 64)), dim3(64), 0, st, own->d_views.p, G);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_tree_ins_leaves, dim3(nblk(k, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, G);
+    LAUNCH_CHECK();
+    if (n_pad) {
+        hipLaunchKernelGGL(k_tree_ins_pad, dim3(nblk(n_pad, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, G);
+        LAUNCH_CHECK();
+    }
+    for (int t = 0; t < H; t++) {
+        const size_t n = plan.merge[t + 1].size() / 5;
+        if (!n) continue;
+        hipLaunchKernelGGL(k_tree_ins_merge, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + plan.merge_off[t + 1],
+                           node_ext + (size_t)(t & 1) * slots * 40, node_ext + (size_t)((t + 1) & 1) * slots * 40, G.pad_ext);
+        LAUNCH_CHECK();
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    own->n_real = 0;
+    own->n_pad = 0;
+    for (int t = 0; t <= H; t++) {
+        own->n_real += own->levels[t].n;
+        if (t < H) own->n_pad += 2 * (uint64_t)own->levels[t + 1].n - own->levels[t].n;
+    }
+    poison.armed = false;
     return DAPOL_OK;
 }
 
@@ -280,7 +373,8 @@ static int32_t tree_remove_incremental(dapol_tree_owned* own, const std::vector<
 // The rebuild path of dapol_tree_update and dapol_tree_remove: the tree's leaf set comes to the host, the edits are merged into it
 // (v == nullptr: removed from it; then leaf_idx is sorted and distinct), and the level-parallel build runs again over the result with
 // the tree's own pad seed and shape -- one pass for the whole batch instead of k root-to-leaf walks.  An error leaves the old tree.
-static int32_t tree_rebuild_edited(dapol_tree_owned* own, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32) {
+// must_be_new (dapol_tree_insert; leaf_idx distinct): an edit of an index that is a leaf already is refused instead of replacing it.
+static int32_t tree_rebuild_edited(dapol_tree_owned* own, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32, bool must_be_new = false) {
     hipStream_t st = own->ctx->stream;
     const size_t n0 = own->levels[0].n;
     HostLeaves old, cur;
@@ -294,6 +388,9 @@ static int32_t tree_rebuild_edited(dapol_tree_owned* own, size_t k, const uint64
             if (!std::binary_search(old.idx.begin(), old.idx.end(), leaf_idx[i])) return fail(DAPOL_ERR_UNKNOWN_LEAF, "an index to remove is not a leaf of the tree (nothing was removed)");
         if (k >= n0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "removing every leaf would leave an empty tree (nothing was removed)");
     }
+    if (must_be_new)
+        for (size_t i = 0; i < k; i++)
+            if (std::binary_search(old.idx.begin(), old.idx.end(), leaf_idx[i])) return fail(DAPOL_ERR_INVALID_ARGUMENT, "an index to insert is already a leaf of the tree (nothing was inserted)");
     merge_leaf_edits(old, k, leaf_idx, v, r32, cur);
     dapol_tree_owned fresh;
     int32_t rc = tree_build_owned(own->ctx, own->index_bits, own->shard_bits, cur.idx.size(), cur.idx.data(), cur.v.data(), cur.r.data(), own->pad_seed, nullptr, 0, &fresh);
@@ -332,9 +429,14 @@ static int32_t tree_edit_end(dapol_tree* tree, int32_t rc) {
 
 // New leaves go in place when there are at most 4,096 of them, all below 2^index_bits and (shard trees) under the shard's prefix;
 // what is out of range is left to the rebuild, which reports the error.
+static int32_t leaves_in_range(dapol_tree_owned* own, const HostLeaves& fresh, bool* ok);
 static int32_t insertable_in_place(dapol_tree_owned* own, const HostLeaves& fresh, bool* ok) {
     *ok = false;
     if (fresh.idx.empty() || fresh.idx.size() > 4096 || own->height < 1 || knob("DAPOL_NO_INCREMENTAL_INSERT")) return DAPOL_OK;
+    return leaves_in_range(own, fresh, ok);
+}
+static int32_t leaves_in_range(dapol_tree_owned* own, const HostLeaves& fresh, bool* ok) {
+    *ok = false;
     for (uint64_t x : fresh.idx) if (own->index_bits < 64 && (x >> own->index_bits)) return DAPOL_OK;
     if (own->shard_bits) {
         uint64_t first = 0;
@@ -387,8 +489,9 @@ int32_t dapol_tree_update(dapol_tree* tree, size_t k, const uint64_t* leaf_idx, 
     int32_t rc = tree_edit_begin(tree, "an update", &own);
     return rc ? rc : tree_edit_end(tree, tree_update_impl(own, k, leaf_idx, v, r32));
 }
-// What the last dapol_tree_update / dapol_tree_remove on this tree did: 0 = rebuilt the tree, 1 = replaced existing leaves in place,
-// 2 = inserted new leaves in place, 3 = both, 4 = removed leaves in place.  (Diagnostics: the result is the same tree whichever path ran.)
+// What the last dapol_tree_update / dapol_tree_insert / dapol_tree_remove on this tree did: 0 = rebuilt the tree, 1 = replaced existing
+// leaves in place, 2 = inserted new leaves in place (disjoint chains), 3 = both, 4 = removed leaves in place, 5 = inserted new leaves in
+// place by the general path (dapol_tree_insert only).  (Diagnostics: the result is the same tree whichever path ran.)
 int32_t dapol_tree_last_update_path(dapol_tree* tree, int32_t* path) {
     if (!tree || !path) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
     *path = static_cast<dapol_tree_owned*>(tree)->last_update_path;
@@ -415,4 +518,55 @@ int32_t dapol_tree_remove(dapol_tree* tree, size_t k, const uint64_t* leaf_idx) 
     dapol_tree_owned* own = nullptr;
     int32_t rc = tree_edit_begin(tree, "a removal", &own);
     return rc ? rc : tree_edit_end(tree, tree_remove_impl(own, k, leaf_idx));
+}
+
+// The general in-place insert is taken up to this many leaves (besides update_incremental_max and an eighth of the tree, the removal's
+// gate).  Measured at 2^20 leaves, height 32 (profiles/tree_insert_2e20_h32.json, medians of 7): 16,384 random new leaves 14.5 ms against
+// 80 ms for the forced rebuild; 65,536, the largest batch the default gate admits, 77 ms against 124 ms (spread of the rebuild 0.31,
+// 39 ms) -- still ahead by more than that spread, so the cap stays where update_incremental_max is.  Where a later measurement finds
+// path 5 no longer ahead of the rebuild by more than the rebuild's spread, this comes down to the largest measured k that is.
+static const size_t INSERT_GENERAL_MAX = 65536;
+// dapol_tree_insert: k NEW leaves, in any order, all or nothing.  The batch is planned once on the device (J1); an index that is a leaf
+// already, or that occurs twice, is refused before anything is written.  Up to 4,096 leaves whose chains share no node take the
+// disjoint-chain insert of dapol_tree_update (path 2: a wavefront per chain); any other batch inside the gate takes the general path
+// (path 5); what is outside it -- or out of range, which the build reports -- is rebuilt (path 0).
+static int32_t tree_insert_impl(dapol_tree_owned* own, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32) {
+    std::vector<size_t> ord(k);
+    for (size_t i = 0; i < k; i++) ord[i] = i;
+    std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return leaf_idx[a] < leaf_idx[b]; });
+    HostLeaves E;
+    for (size_t b = 0; b < k; b++) {
+        if (b && leaf_idx[ord[b]] == leaf_idx[ord[b - 1]]) return fail(DAPOL_ERR_INVALID_ARGUMENT, "an index occurs twice in the batch to insert (nothing was inserted)");
+        E.push(leaf_idx[ord[b]], v[ord[b]], r32 + (size_t)ord[b] * 32);
+    }
+    const size_t n0 = own->levels[0].n;
+    bool in_range = false;
+    if (own->height >= 1 && k <= incremental_max(own->ctx) && k <= INSERT_GENERAL_MAX && k <= n0 / 8 + 1 && n0 + k <= ((size_t)1 << 31)) {
+        int32_t rc = leaves_in_range(own, E, &in_range);
+        if (rc != DAPOL_OK) return rc;
+    }
+    if (in_range) {
+        InsPlanRead R;
+        int32_t rc = insert_plan_all(own, E, R);
+        if (rc != DAPOL_OK) return rc;
+        if (R.flag & 2u) return fail(DAPOL_ERR_INVALID_ARGUMENT, "an index to insert is already a leaf of the tree (nothing was inserted)");
+        bool done = false;
+        if (k <= 4096 && !(R.flag & 1u)) {
+            rc = tree_insert_incremental(own, E, &done, &R);
+            if (rc != DAPOL_OK) return rc;
+            if (done) { own->last_update_path = 2; return DAPOL_OK; }
+        }
+        rc = tree_insert_general(own, E, R);
+        if (rc != DAPOL_OK) return rc;
+        own->last_update_path = 5;
+        return DAPOL_OK;
+    }
+    return tree_rebuild_edited(own, k, leaf_idx, v, r32, true);
+}
+int32_t dapol_tree_insert(dapol_tree* tree, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32) {
+    if (!tree || (k && (!leaf_idx || !v || !r32))) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return DAPOL_OK;
+    dapol_tree_owned* own = nullptr;
+    int32_t rc = tree_edit_begin(tree, "an insert", &own);
+    return rc ? rc : tree_edit_end(tree, tree_insert_impl(own, k, leaf_idx, v, r32));
 }

@@ -713,6 +713,164 @@ __global__ __launch_bounds__(64) void k_tree_ins_chain(TableView tbl, const Leve
     }
 }
 
+// ------------------------------------------------------------------------------------- incremental insert, general
+// dapol_tree_insert's in-place path for ANY batch of new leaves: chains may share nodes (a sibling pair, a whole new subtree), which
+// the wavefront-per-chain prefix sums of I3 cannot express.  It is the removal's mirror image: the host plans the forest
+// (plan_insert_general), the levels that gain nodes are rewritten by k_tree_relayout, and every FRESH node -- a new one, or an existing
+// ancestor of a new leaf -- is merged from its children level by level, bottom-up.
+//   J1  k_tree_ins_plan_all  per new leaf: as I1, continued to the root: the lower bound of x >> t at EVERY level
+//   J2  k_tree_relayout      per level that gains nodes (existing nodes only)
+//   J3  k_tree_ins_struct    per new node: idx, parent, has_pad = 0; a chain top also clears has_pad of its real sibling S
+//   J4  k_tree_ins_leaves    per new leaf: v*B + r*B_blinding, its record, its extended point
+//   J5  k_tree_ins_pad       per new node with a padding sibling: k_tree_rm_pad's record, and its extended point
+//   J6  k_tree_ins_merge     per level: every fresh node = Mergeable::merge of its children
+// A point this call has produced is never decoded again: J4 - J6 leave the extended point of every fresh node and every new padding
+// node in the call's scratch (160 bytes a slot; node slots alternate between two halves by level parity), and a merge reads a child
+// made by this call from there.  Only an untouched existing sibling, or an existing padding record, is decoded from its 32 bytes.
+// On the private part of a new chain both children are fresh, so a merge pays one encoding and no decoding -- k_tree_rm_merge pays
+// two decodings and an encoding, each an inverse square root, on what is a serial chain of single-lane launches for a small batch.
+// Compiler report, gfx950 (VGPRs / scratch bytes a lane): k_tree_ins_plan_all 36 / 0; k_tree_ins_struct 22 / 0; k_tree_ins_leaves
+// 178 / 448; k_tree_ins_pad 188 / 448; k_tree_ins_merge 226 / 624 (k_tree_rm_merge: 186 / 800) -- two waves a SIMD for the three that
+// hold a point, which a launch of a few lanes does not notice and a launch of thousands shares with the build's own kernels.
+// J1: k_tree_ins_plan (same arguments) that does not stop at the first existing ancestor: inspos[j][t] is written for every t <= height.
+// (It searches every level; above m the parent pointers would give the same positions for one load a level -- not done yet, see
+// DESIGN.md 4.3 on the 0.1 ms this costs a small batch.)
+// conflict bit 1 (chains that share a node) only selects the path here; bit 2 = an index that is a leaf already.
+__global__ __launch_bounds__(64) void k_tree_ins_plan_all(const LevelView* views, TreeInsPlan P) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= P.k) return;
+    const uint64_t x = P.idx[j];
+    uint32_t* out = P.inspos + j * (size_t)(P.height + 1);
+    int m = -1;
+    for (int t = 0; t <= P.height; t++) {
+        const LevelView L = views[t];
+        const uint64_t want = t < 64 ? x >> t : 0;
+        size_t lo = 0, hi = L.n;
+        while (lo < hi) {
+            const size_t mid = (lo + hi) >> 1;
+            if (L.idx[mid] < want) lo = mid + 1; else hi = mid;
+        }
+        out[t] = (uint32_t)lo;
+        if (m < 0 && lo < L.n && L.idx[lo] == want) m = t;
+    }
+    if (m < 0) m = P.height;
+    P.m[j] = (uint32_t)m;
+    if (m == 0) atomicOr(P.conflict, 2u);          // the leaf exists
+    if (j > 0) {                                    // shares a new node with its left neighbour?
+        const uint64_t y = P.idx[j - 1];
+        for (int t = 0; t < m; t++)
+            if ((t < 64 ? x >> t : 0) == (t < 64 ? y >> t : 0)) { atomicOr(P.conflict, 1u); break; }
+    }
+}
+struct TreeInsGeneral {
+    size_t n_new, k, n_pad;
+    const uint32_t *lvl, *pos, *parent, *sib, *idx_lo, *idx_hi;    // [n_new]: the new nodes (plan_insert_general's n_*)
+    const uint32_t* leaf_pos;                                       // [k]
+    const uint32_t *pad_lvl, *pad_pos;                              // [n_pad]
+    const uint64_t* v; const uint32_t* r;                           // [k], [k][8]: the new leaves, sorted by index
+    const uint32_t* pad_seed;                                       // [8]
+    int32_t* node_ext;                                              // [2][slots][40]: fresh nodes, half = level & 1
+    int32_t* pad_ext;                                               // [n_pad][40]
+    uint32_t slots;
+};
+// J3
+__global__ __launch_bounds__(64) void k_tree_ins_struct(const LevelView* views, TreeInsGeneral G) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= G.n_new) return;
+    const LevelView L = views[G.lvl[i]];
+    const size_t d = G.pos[i];
+    L.idx[d] = (uint64_t)G.idx_lo[i] | ((uint64_t)G.idx_hi[i] << 32);
+    L.parent[d] = G.parent[i];
+    L.has_pad[d] = 0;
+    if (G.sib[i] != 0xffffffffu) L.has_pad[G.sib[i]] = 0;          // a chain top: S's padding sibling (at this node's position) goes away
+}
+// J4
+__global__ __launch_bounds__(64) void k_tree_ins_leaves(TableView tbl, const LevelView* views, TreeInsGeneral G) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= G.k) return;
+    const LevelView L = views[0];
+    const size_t d = G.leaf_pos[j];
+    uint32_t rl[8], c[8], h[8];
+    ld8(rl, G.r + j * 8);
+    rl[7] &= 0x7fffffffu;                          // Scalar::from_bits; the leaf keeps its blinding as given (possibly >= l)
+    ge_p3 P0;
+    ge_identity(P0);
+    tbl_fixed_mul_add_u64(P0, tbl, tbl.row_B(0), G.v[j]);
+    tbl_fixed_mul_add(P0, tbl, tbl.row_Bb(0), rl);
+    ge_compress(c, P0);
+    node_hash32(tbl.digest, h, c);
+    L.v[d] = G.v[j];
+    st8(L.r + d * 8, rl);
+    st8(L.C + d * 8, c);
+    st8(L.H + d * 8, h);
+    st_p3(G.node_ext + j * 40, P0);
+}
+// J5: k_tree_rm_pad for the new node at (pad_lvl[i], pad_pos[i]), which also keeps the padding node's extended point.
+__global__ __launch_bounds__(64) void k_tree_ins_pad(TableView tbl, const LevelView* views, TreeInsGeneral G) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= G.n_pad) return;
+    const int t = (int)G.pad_lvl[i];
+    const size_t s = G.pad_pos[i];
+    const LevelView L = views[t];
+    uint32_t seed[8], wide[16], rB[8], cB[8], hB[8];
+    for (int k = 0; k < 8; k++) seed[k] = G.pad_seed[k];
+    seed_wide(wide, seed, 1u, (uint64_t)t, L.idx[s] ^ 1ull);
+    sc rm;
+    sc_from_wide(rm, wide);
+    sc_from_mont(rB, rm);
+    ge_p3 pB;
+    ge_identity(pB);
+    tbl_fixed_mul_add(pB, tbl, tbl.row_Bb(0), rB);
+    ge_compress(cB, pB);
+    node_hash32(tbl.digest, hB, cB);
+    st8(L.padC + s * 8, cB);
+    st8(L.padH + s * 8, hB);
+    st8(L.padr + s * 8, rB);
+    L.has_pad[s] = 1;
+    st_p3(G.pad_ext + i * 40, pB);
+}
+// J6, one level: e[5 i ..] = position of a fresh node in nxt | position of its first fresh child in cur | the node's slot | the
+// child's slot | the other child: a slot of cur's half, 0x80000000 | pad slot, or 0xffffffff = decode it.  The pairing, the hash
+// order, the u64 wrap and r mod l are k_tree_rm_merge's.
+__global__ __launch_bounds__(64) void k_tree_ins_merge(int digest, LevelView cur, LevelView nxt, size_t n, const uint32_t* e, const int32_t* ext_cur,
+                                                       int32_t* ext_nxt, const int32_t* pad_ext) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const size_t p = e[5 * i], c = e[5 * i + 1];
+    const uint32_t slot_p = e[5 * i + 2], slot_c = e[5 * i + 3], other = e[5 * i + 4];
+    const bool left = (cur.idx[c] & 1ull) == 0;
+    uint32_t cA[8], hA[8], rA[8], cB[8], hB[8], rB[8];
+    const uint64_t vA = cur.v[c];
+    uint64_t vB = 0;
+    ld8(cA, cur.C + c * 8); ld8(hA, cur.H + c * 8); ld8(rA, cur.r + c * 8);
+    if (cur.has_pad[c]) { ld8(cB, cur.padC + c * 8); ld8(hB, cur.padH + c * 8); ld8(rB, cur.padr + c * 8); }
+    else {
+        const size_t s = left ? c + 1 : c - 1;
+        ld8(cB, cur.C + s * 8); ld8(hB, cur.H + s * 8); ld8(rB, cur.r + s * 8);
+        vB = cur.v[s];
+    }
+    ge_p3 pA, pB, pp;
+    ld_p3(pA, ext_cur + (size_t)slot_c * 40);
+    if (other == 0xffffffffu) (void)ge_decompress(pB, cB);          // the tree's own encoding: always decodes
+    else if (other & 0x80000000u) ld_p3(pB, pad_ext + (size_t)(other & 0x7fffffffu) * 40);
+    else ld_p3(pB, ext_cur + (size_t)other * 40);
+    ge_add(pp, pA, pB);
+    sc ma, mb, ms;
+    sc_to_mont(ma, rA);
+    sc_to_mont(mb, rB);
+    sc_add(ms, ma, mb);
+    uint32_t rp[8], cp[8], hp[8];
+    sc_from_mont(rp, ms);
+    ge_compress(cp, pp);
+    if (left) node_hash128(digest, hp, cA, cB, hA, hB);
+    else node_hash128(digest, hp, cB, cA, hB, hA);
+    nxt.v[p] = vA + vB;                            // u64 wrap == release-mode Rust (node.rs:72)
+    st8(nxt.r + p * 8, rp);
+    st8(nxt.C + p * 8, cp);
+    st8(nxt.H + p * 8, hp);
+    st_p3(ext_nxt + (size_t)slot_p * 40, pp);
+}
+
 // ------------------------------------------------------------------------------------- incremental remove
 // Removing leaves (dapol_tree_remove) is the mirror image of the insert.  A real node dies iff all its real children die (a node
 // whose has_pad is set has one real child); the dead nodes of a removed leaf form a chain from the leaf up to a CHAIN TOP whose

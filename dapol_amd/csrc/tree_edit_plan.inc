@@ -165,3 +165,104 @@ static RemovePlan plan_remove(int H, size_t k, const uint64_t* si, const uint32_
     P.merge_off.push_back(P.flat.size());
     return P;
 }
+
+// In-place insert of k new leaves in general -- chains may share nodes (a sibling pair, a whole new subtree) -- from what
+// k_tree_ins_plan_all returns: x = the indexes, sorted and distinct; m[j] = length of leaf j's chain of new nodes; pos_all[j][t] = the
+// old-layout lower bound of x[j] >> t at every level t <= H (for t >= m[j] the ancestor's exact position).  Rows have H + 1 entries.
+//   The FRESH nodes of level t are the distinct x[j] >> t in ascending order: the new ones (t < m[j]) and, above them, the existing
+// ancestors the call has to merge again.  A fresh node's position in the new layout is its lower bound plus the number of NEW nodes
+// before it in that list (for an existing node these are exactly the new nodes with a smaller index).  A new node has a padding
+// sibling iff its parent is new and its sibling is not; a new node whose parent exists is a TOP: its sibling S is an existing real
+// node, adjacent in the sorted level, which carries the padding record of the top's position and loses has_pad.  Every fresh node
+// above the leaves is merged from its children; a fresh node's slot (where its extended point waits for the merge above) is its rank
+// in its level's fresh list, a padding node's slot its rank in the pad list.
+struct InsertGeneralPlan {
+    enum : uint32_t { NONE = 0xffffffffu, PAD_SLOT = 0x80000000u };
+    int D = 0;                                   // levels 0 .. D - 1 gain nodes
+    uint32_t max_fresh = 0;                      // the longest fresh list (slots per level)
+    std::vector<std::vector<uint32_t>> gain;     // [H + 1]: old-layout lower bounds of the level's new nodes, ascending
+    // per new node, level by level bottom-up, index ascending
+    std::vector<uint32_t> n_lvl, n_pos, n_parent, n_sib;     // level | new position | parent's new position | tops: S's new position, else NONE
+    std::vector<uint64_t> n_idx;
+    std::vector<uint8_t> n_has_pad;
+    std::vector<uint32_t> leaf_pos;              // [k]: new position of leaf j (its slot is j)
+    std::vector<uint32_t> pad_lvl, pad_pos;      // the new nodes that take a padding sibling, in the order above; pad slot = rank here
+    // [H + 1], level t >= 1: five words per fresh node of the level --
+    //   its new position | new position of its first fresh child (level t - 1) | its slot | that child's slot |
+    //   the other child: a slot of level t - 1 (fresh too), PAD_SLOT | pad slot (the child's new padding sibling), or NONE (an
+    //   untouched node or an old padding record: decoded from the level's arrays)
+    std::vector<std::vector<uint32_t>> merge;
+    // one upload: 8 words for the pad seed | gain lists | n_lvl | n_pos | n_parent | n_sib | n_idx lo | n_idx hi | leaf_pos | pad_lvl | pad_pos | merge lists
+    std::vector<uint32_t> flat;
+    std::vector<size_t> gain_off, merge_off;     // [H + 2]: list t is flat[off[t] .. off[t + 1])
+    size_t lvl_off = 0, pos_off = 0, parent_off = 0, sib_off = 0, idx_lo_off = 0, idx_hi_off = 0, leaf_off = 0, pad_lvl_off = 0, pad_pos_off = 0;
+};
+static InsertGeneralPlan plan_insert_general(int H, size_t k, const uint64_t* x, const uint32_t* m, const uint32_t* pos_all) {
+    const size_t S1 = (size_t)H + 1;
+    InsertGeneralPlan P;
+    P.gain.resize(S1); P.merge.resize(S1);
+    auto shr = [](uint64_t a, int t) { return t < 64 ? a >> t : (uint64_t)0; };
+    struct Fresh { uint32_t rep, pos; bool is_new; uint32_t node; };     // rep = the first new leaf under it; node = its row in n_* (new nodes)
+    std::vector<Fresh> cur, nxt;
+    auto fresh_of = [&](int t, std::vector<Fresh>& out) {
+        out.clear();
+        uint32_t n_new = 0;
+        for (size_t j = 0; j < k; j++) {
+            if (j > 0 && shr(x[j], t) == shr(x[j - 1], t)) continue;
+            const bool is_new = t < (int)m[j];
+            const uint32_t lb = pos_all[j * S1 + t];
+            out.push_back({(uint32_t)j, lb + n_new, is_new, InsertGeneralPlan::NONE});
+            if (is_new) { P.gain[t].push_back(lb); n_new++; }
+        }
+    };
+    fresh_of(0, cur);
+    for (int t = 0; t <= H; t++) {
+        if (t < H) fresh_of(t + 1, nxt); else nxt.clear();
+        P.max_fresh = std::max(P.max_fresh, (uint32_t)cur.size());
+        // parents: fresh node a of level t hangs under nxt[q], q advancing with the parent's index
+        size_t q = 0;
+        for (size_t a = 0; a < cur.size(); a++) {
+            Fresh& c = cur[a];
+            const uint64_t me = shr(x[c.rep], t);
+            if (t < H) while (shr(x[nxt[q].rep], t + 1) != me >> 1) q++;
+            if (t == 0) P.leaf_pos.push_back(c.pos);
+            if (!c.is_new) continue;
+            const bool sib_new = (a > 0 && cur[a - 1].is_new && shr(x[cur[a - 1].rep], t) == (me ^ 1)) ||
+                                 (a + 1 < cur.size() && cur[a + 1].is_new && shr(x[cur[a + 1].rep], t) == (me ^ 1));
+            const bool parent_new = nxt[q].is_new;            // (a new node is never the root: t < m <= H)
+            const bool has_pad = parent_new && !sib_new;
+            c.node = (uint32_t)P.n_pos.size();
+            P.n_lvl.push_back((uint32_t)t); P.n_pos.push_back(c.pos); P.n_idx.push_back(me); P.n_parent.push_back(nxt[q].pos);
+            P.n_sib.push_back(parent_new ? InsertGeneralPlan::NONE : (me & 1) ? c.pos - 1 : c.pos + 1);
+            P.n_has_pad.push_back(has_pad);
+            if (has_pad) { P.pad_lvl.push_back((uint32_t)t); P.pad_pos.push_back(c.pos); }
+        }
+        if (t == H) break;
+        // merges of level t + 1: the one or two fresh children of every fresh node there
+        uint32_t pad_slot = (uint32_t)P.pad_pos.size();
+        for (size_t a = cur.size(); a-- > 0;) if (cur[a].is_new && P.n_has_pad[cur[a].node]) cur[a].node = --pad_slot; else cur[a].node = InsertGeneralPlan::NONE;   // node := pad slot
+        for (size_t a = 0, qq = 0; a < cur.size(); qq++) {
+            const uint64_t par = shr(x[cur[a].rep], t) >> 1;
+            const bool two = a + 1 < cur.size() && (shr(x[cur[a + 1].rep], t) >> 1) == par;
+            const uint32_t other = two ? (uint32_t)(a + 1) : cur[a].node != InsertGeneralPlan::NONE ? (InsertGeneralPlan::PAD_SLOT | cur[a].node) : InsertGeneralPlan::NONE;
+            const uint32_t e[5] = {nxt[qq].pos, cur[a].pos, (uint32_t)qq, (uint32_t)a, other};
+            P.merge[t + 1].insert(P.merge[t + 1].end(), e, e + 5);
+            a += two ? 2 : 1;
+        }
+        std::swap(cur, nxt);
+    }
+    while (P.D < H && !P.gain[P.D].empty()) P.D++;
+    P.flat.assign(8, 0);
+    auto put = [&](const std::vector<uint32_t>& v) { const size_t o = P.flat.size(); P.flat.insert(P.flat.end(), v.begin(), v.end()); return o; };
+    for (auto& g : P.gain) P.gain_off.push_back(put(g));
+    P.gain_off.push_back(P.flat.size());
+    P.lvl_off = put(P.n_lvl); P.pos_off = put(P.n_pos); P.parent_off = put(P.n_parent); P.sib_off = put(P.n_sib);
+    P.idx_lo_off = P.flat.size();
+    for (uint64_t i : P.n_idx) P.flat.push_back((uint32_t)i);
+    P.idx_hi_off = P.flat.size();
+    for (uint64_t i : P.n_idx) P.flat.push_back((uint32_t)(i >> 32));
+    P.leaf_off = put(P.leaf_pos); P.pad_lvl_off = put(P.pad_lvl); P.pad_pos_off = put(P.pad_pos);
+    for (auto& g : P.merge) P.merge_off.push_back(put(g));
+    P.merge_off.push_back(P.flat.size());
+    return P;
+}

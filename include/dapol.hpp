@@ -5,6 +5,7 @@
 //   panics                 -> throws dapol::DapolError{code 8}   (src/range/padding.rs:95-98, smtree build)
 // Header-only; link with -ldapol_hip.  No computation happens here.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstdio>
@@ -345,6 +346,29 @@ class Dapol {
             return;
         }
         check(dapol_tree_update(tree_.get(), idx.size(), idx.data(), values.data(), blindings[0].data()));
+    }
+    // Adds NEW liabilities at these leaf indexes (dapol_tree_insert; in any order, all or nothing): the tree equals a build over the old
+    // and the new leaves with the same seed.  An index that is a leaf already (or given twice) throws
+    // DapolError(DAPOL_ERR_INVALID_ARGUMENT) with nothing inserted.  On a blank Dapol it builds over the whole batch (sorted here; all or nothing too).  There is no insert by
+    // liability id: build_leaf_nodes' collision rule runs over the whole ordered liability list and has no "insert into an existing
+    // set" form.
+    void insert(const std::vector<uint64_t>& idx, const std::vector<uint64_t>& values, const std::vector<Bytes32>& blindings) {
+        insert(idx, values, blindings, tree_ ? Bytes32{} : get_secret());
+    }
+    void insert(const std::vector<uint64_t>& idx, const std::vector<uint64_t>& values, const std::vector<Bytes32>& blindings, const Bytes32& pad_seed) {
+        if (idx.size() != values.size() || idx.size() != blindings.size()) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        if (idx.empty()) return;
+        if (tree_) return check(dapol_tree_insert(tree_.get(), idx.size(), idx.data(), values.data(), blindings[0].data()));
+        std::vector<size_t> ord(idx.size());                         // a blank Dapol: one build over the whole batch, all or nothing as well
+        for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+        std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return idx[a] < idx[b]; });
+        std::vector<uint64_t> si, sv;
+        std::vector<Bytes32> sr;
+        for (size_t b = 0; b < ord.size(); b++) {
+            if (b && idx[ord[b]] == idx[ord[b - 1]]) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+            si.push_back(idx[ord[b]]); sv.push_back(values[ord[b]]); sr.push_back(blindings[ord[b]]);
+        }
+        build(si, sv, sr, pad_seed);
     }
     // Removes the liabilities at these leaf indexes (dapol_tree_remove; the crate has no removal): all or nothing, the survivors keep
     // their indexes, and the tree equals a build over the survivors with the same seed.  An index that is not a leaf throws

@@ -217,8 +217,22 @@ int32_t dapol_tree_update(dapol_tree* tree, size_t k, const uint64_t* leaf_idx, 
  * between the first and the last write of such a removal marks the tree invalid, as for dapol_tree_update.  Larger batches rebuild
  * the tree from the surviving leaves (an error then leaves the old tree as it was). */
 int32_t dapol_tree_remove(dapol_tree* tree, size_t k, const uint64_t* leaf_idx);
-/* What the last dapol_tree_update / dapol_tree_remove on this tree did: 0 = rebuilt, 1 = replaced existing leaves in place, 2 = inserted
- * new leaves in place, 3 = both, 4 = removed leaves in place (diagnostics; the tree is the same whichever path ran). */
+/* Adds k NEW leaves, given in any order (k = 0 does nothing); the counterpart of dapol_tree_remove.  All or nothing.  Afterwards the
+ * tree equals dapol_tree_build (dapol_tree_build_shard) over (old leaves + new leaves) with the tree's pad seed bit for bit, at every
+ * level -- node counts, padding records and parent pointers included -- whichever path ran.  A leaf keeps its blinding as given
+ * (bit 255 cleared, possibly >= l); parents hold the reduced sums.  An index that is a leaf already, or that occurs twice in the batch
+ * -> DAPOL_ERR_INVALID_ARGUMENT with nothing written and the tree usable (dapol_last_error says which); an index outside the tree or
+ * outside a shard's prefix is refused with dapol_tree_update's code for the same batch, the tree unchanged.  Refused like
+ * dapol_tree_update: trees built from a padding tape, workload trees, trees marked invalid.  Batches within update_incremental_max
+ * (dapol_options) and at most an eighth of the leaves go IN PLACE on the device, whatever nodes their chains share (a sibling pair, a
+ * whole new subtree): the levels that gain nodes are rewritten in order and only the new nodes and the ancestors of the new leaves
+ * are merged.  A HIP failure between the first and the last write of such an insert marks the tree invalid, as for
+ * dapol_tree_update.  Larger batches rebuild the tree (an error then leaves the old tree as it was).  dapol_tree_update keeps
+ * rebuilding for new leaves whose chains share a node; a caller that only ADDS leaves should call this instead. */
+int32_t dapol_tree_insert(dapol_tree* tree, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32);
+/* What the last dapol_tree_update / dapol_tree_insert / dapol_tree_remove on this tree did: 0 = rebuilt, 1 = replaced existing leaves
+ * in place, 2 = inserted new leaves in place (disjoint chains), 3 = both, 4 = removed leaves in place, 5 = inserted new leaves in place
+ * by dapol_tree_insert's general path (diagnostics; the tree is the same whichever path ran). */
 int32_t dapol_tree_last_update_path(dapol_tree* tree, int32_t* path);
 /* Dapol::root_raw / Dapol::root (src/dapol/mod.rs:134-141). Any out pointer may be NULL. */
 int32_t dapol_tree_root(dapol_tree* tree, uint8_t C32[32], uint8_t H32[32], uint64_t* v, uint8_t r32[32]);
