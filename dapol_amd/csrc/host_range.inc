@@ -483,6 +483,7 @@ __global__ void k_gather_parties(size_t b, int height, int start, int count, int
     st8(Vc + t * 8, c);
 }
 
+static bool policy_grouping_on() { return !knob("DAPOL_NO_GROUP"); }      // prover and verifier alike (policy_plan.inc: group_policy_plan)
 // R::generate_proof (src/range/padding.rs:88-118, splitting.rs:100-129) for b proofs over H siblings each: pv / pr / pC
 // are [b][H] device arrays of the siblings' values, blindings and commitments; one RNG stream (d_stream[e]) per proof
 // runs across its sub-proofs.  d_range: [b][sum of the plan's proof words].
@@ -495,19 +496,9 @@ static int32_t prove_policy_device(dapol_ctx* ctx, const std::vector<SubProof>& 
     hipStream_t st = ctx->stream;
     size_t entity_words = 0;
     for (auto& s : plan) entity_words += dapol_range_proof_size(n_bits, s.m) / 4;
-    struct Group { int start, count, m, k; };
-    std::vector<Group> groups;
-    const bool group = !knob("DAPOL_NO_GROUP");
-    for (auto& s : plan) {
-        if (group && !groups.empty() && groups.back().m == s.m && groups.back().count == s.m && s.count == s.m &&
-            groups.back().start + groups.back().k * s.m == s.start) groups.back().k++;
-        else groups.push_back({s.start, s.count, s.m, 1});
-    }
-    size_t max_parties = 1, sum_parties = 0, sum_proofs = 0;
-    for (auto& g : groups) {
-        if ((size_t)g.m * (size_t)g.k > max_parties) max_parties = (size_t)g.m * (size_t)g.k;
-        sum_parties += (size_t)g.m * (size_t)g.k; sum_proofs += (size_t)g.k;
-    }
+    const PolicyGroups PG = group_policy_plan(plan, policy_grouping_on());
+    const std::vector<PolicyGroup>& groups = PG.groups;
+    const size_t max_parties = PG.max_parties, sum_parties = PG.sum_parties, sum_proofs = PG.sum_proofs;
     const uint32_t* Bb_comp = ctx->gens_comp.p + (size_t)ctx->tv.row_Bb(0) * 8;
     // A SMALL call whose plan has several groups (splitting at aggregation 24 = a 16-party and an 8-party proof: one of the reference's
     // six `prove` cases, benches/dapol.rs:71-78; any plan with individual proofs) is a chain of latencies per group, and the groups are

@@ -33,6 +33,31 @@ static bool policy_plan(int policy, int n_siblings, int agg, std::vector<SubProo
     return true;
 }
 
+// A run of the plan's equal-sized FULL sub-proofs (the individual proofs beyond aggregation_factor, with the one-party part of an odd
+// split before them) is ONE group of k proofs per entity: the prover proves it in one call, the verifier checks it in one batch, and
+// the two must agree on it.  group = false: every sub-proof is a group of its own (DAPOL_NO_GROUP).
+struct PolicyGroup { int start, count, m, k; };
+struct PolicyGroups {
+    std::vector<PolicyGroup> groups;
+    size_t sum_proofs = 0, sum_parties = 0;                 // sub-proofs and parties per entity, over all groups
+    size_t max_k = 1, max_parties = 1;                      // most sub-proofs / most parties (k * m) of one group
+};
+static PolicyGroups group_policy_plan(const std::vector<SubProof>& plan, bool group) {
+    PolicyGroups G;
+    for (auto& s : plan) {
+        if (group && !G.groups.empty() && G.groups.back().m == s.m && G.groups.back().count == s.m && s.count == s.m &&
+            G.groups.back().start + G.groups.back().k * s.m == s.start) G.groups.back().k++;
+        else G.groups.push_back({s.start, s.count, s.m, 1});
+    }
+    for (auto& g : G.groups) {
+        const size_t k = (size_t)g.k, parties = k * (size_t)g.m;
+        G.sum_proofs += k; G.sum_parties += parties;
+        if (k > G.max_k) G.max_k = k;
+        if (parties > G.max_parties) G.max_parties = parties;
+    }
+    return G;
+}
+
 size_t dapol_entity_proof_size(int32_t height, int32_t policy, int32_t aggregation_factor, int32_t n_bits) {
     std::vector<SubProof> plan;
     if (!policy_plan(policy, height, aggregation_factor, plan)) return 0;
