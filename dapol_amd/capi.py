@@ -118,6 +118,9 @@ _SIG = {
     "dapol_shared_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),
     "dapol_prove_entities_shared": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
                                                      _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dapol_reprove_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
+    "dapol_reprove_entities_shared": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P,
+                                                       _P, _P]),
     "dapol_workload_create": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_create_shard": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_build": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(WorkloadStats)]),
@@ -494,6 +497,21 @@ def shared_plan(height, leaf_idx, policy, aggregation_factor):
     return n_sub[:per.value // b if b else 0], int(tot.value), int(per.value)
 
 
+def reprove_plan(height, leaf_idx, edited_idx, policy, aggregation_factor, has_old=None):
+    """dapol_reprove_plan (host-only): what reprove_entities_shared would prove after the leaves `edited_idx` (replaced, inserted and
+    removed ones, strictly increasing) changed: (heads per sub-proof of the plan, their sum, the sum of m over them, the sum of m over
+    shared_plan's statements).  leaf_idx = the tree's leaves as they are now; has_old[e] = 0 marks newly inserted ones."""
+    leaf_idx, edited_idx = _u64(leaf_idx), _u64(edited_idx)
+    b = leaf_idx.shape[0]
+    ho = None if has_old is None else _u8(has_old, b)
+    n_sub = np.zeros(max(height, 0) + 2, np.uint64)              # a plan has at most height + 1 sub-proofs
+    tot, sm, sm_shared = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _chk(lib().dapol_reprove_plan(height, b, _ptr(leaf_idx), _ptr(ho), edited_idx.shape[0], _ptr(edited_idx), policy, aggregation_factor, _ptr(n_sub),
+                                  ctypes.byref(tot), ctypes.byref(sm), ctypes.byref(sm_shared)))
+    plan_size = (1 if policy == POLICY_PADDING else bin(aggregation_factor).count("1")) + height - aggregation_factor
+    return n_sub[:plan_size], int(tot.value), int(sm.value), int(sm_shared.value)
+
+
 COMM_ID_BYTES, RECORD_BYTES = 128, 104
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 
@@ -755,6 +773,31 @@ class Tree:
         _chk(lib().dapol_prove_entities_shared(self.ctx.h, self.h, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(seed), nu,
                                                _ptr(uC), _ptr(uH), _ptr(uv), _ptr(ur), _ptr(C), _ptr(H), _ptr(out), ctypes.byref(unique)))
         return C, H, out, int(unique.value)
+
+    def reprove_entities_shared(self, leaf_idx, old_leaf_idx, old_path_C, old_blobs, policy, aggregation_factor, n_bits, nonce_seed):
+        """dapol_reprove_entities_shared: prove_entities_shared's outputs for the tree as it is now, proving only the sub-proofs whose
+        sibling commitments differ from old_path_C; the others keep the bytes of old_blobs.  old_leaf_idx (strictly increasing) names
+        the rows of old_path_C [n][H][32] / old_blobs [n][entity bytes]: they are aligned to leaf_idx here (np.searchsorted), rows of
+        leaves that are gone are dropped, and a leaf without an old row is proved from scratch.  old_leaf_idx = None: no old data.
+        Returns (path_C, path_H, blobs, range proofs actually computed, (sub-proof, entity) pairs kept)."""
+        leaf_idx = _u64(leaf_idx)
+        b, h = leaf_idx.shape[0], self.height
+        es = lib().dapol_entity_proof_size(h, policy, aggregation_factor, n_bits)
+        C, H = np.zeros((b, h, 32), np.uint8), np.zeros((b, h, self.ctx.hb), np.uint8)
+        out = np.zeros((b, max(es, 1)), np.uint8)
+        seed = _u8(np.frombuffer(nonce_seed, np.uint8))
+        has_old, oC, oR = np.zeros(max(b, 1), np.uint8), None, None
+        if old_leaf_idx is not None and len(old_leaf_idx) and b:
+            old_leaf_idx = _u64(old_leaf_idx)
+            n = old_leaf_idx.shape[0]
+            src_C, src_R = _u8(old_path_C, n, h, 32), _u8(old_blobs, n, max(es, 1))
+            at = np.minimum(np.searchsorted(old_leaf_idx, leaf_idx), n - 1)
+            has_old = (old_leaf_idx[at] == leaf_idx).astype(np.uint8)
+            oC, oR = np.ascontiguousarray(src_C[at]), np.ascontiguousarray(src_R[at])
+        proved, kept = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _chk(lib().dapol_reprove_entities_shared(self.ctx.h, self.h, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(seed), _ptr(has_old),
+                                                 _ptr(oC), _ptr(oR), _ptr(C), _ptr(H), _ptr(out), ctypes.byref(proved), ctypes.byref(kept)))
+        return C, H, out, int(proved.value), int(kept.value)
 
 
 class Workload:

@@ -20,6 +20,7 @@
 #include "kernels_leaf.h"
 #include "kernels_shared.h"
 #include "kernels_verify_shared.h"
+#include "kernels_reprove.h"
 
 using namespace dapol;
 
@@ -447,6 +448,7 @@ int32_t dapol_commit_hash_batch(dapol_ctx* ctx, size_t n, const uint64_t* v, con
 #include "host_tree_edit.inc"
 #include "host_range.inc"
 #include "host_shared.inc"
+#include "host_reprove.inc"
 #include "host_verify_shared.inc"
 #include "host_leaf.inc"
 #include "host_wire.inc"

@@ -54,14 +54,11 @@ static int32_t inclusive_scan_u32(hipStream_t st, const uint32_t* in, uint32_t* 
     return DAPOL_OK;
 }
 
-// The shared counterpart of prove_policy_device: pv / pr / pC are the gathered [b][H] siblings, d_idx the b ascending leaf indexes.
-static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t b, int H, const uint64_t* pv, const uint32_t* pr,
-                                          const uint32_t* pC, int n_bits, const uint32_t* d_seed, const uint64_t* d_idx, uint32_t* d_range,
-                                          uint64_t* unique_out) {
-    hipStream_t st = ctx->stream;
+// The plan as the kernels take it: key shifts, sibling spans, and the GROUPS (runs of equal m) with their places inside an entity's blob.
+static int32_t shared_plan_dev_build(const std::vector<SubProof>& plan, size_t b, int H, int n_bits, SharedPlanDev& P) {
     if (plan.size() > SHARED_MAX_SUB || (uint64_t)b * (plan.size() + 1) >= (1ull << 32))
         return fail(DAPOL_ERR_INVALID_ARGUMENT, "too many sub-proofs in one call (entities x plan size must stay below 2^32)");
-    SharedPlanDev P{};
+    P = SharedPlanDev{};
     P.n_sub = (uint32_t)plan.size(); P.H = (uint32_t)H;
     shared_shifts(plan, H, g_wire.siblings_leaf_first != 0, P.shift);
     uint32_t q = 0;
@@ -77,6 +74,17 @@ static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubP
         q += pieces;
     }
     P.entity_pieces = q;
+    return DAPOL_OK;
+}
+
+// The shared counterpart of prove_policy_device: pv / pr / pC are the gathered [b][H] siblings, d_idx the b ascending leaf indexes.
+static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t b, int H, const uint64_t* pv, const uint32_t* pr,
+                                          const uint32_t* pC, int n_bits, const uint32_t* d_seed, const uint64_t* d_idx, uint32_t* d_range,
+                                          uint64_t* unique_out) {
+    hipStream_t st = ctx->stream;
+    SharedPlanDev P;
+    int32_t rc = shared_plan_dev_build(plan, b, H, n_bits, P);
+    if (rc) return rc;
     // heads and ranks: rank[s][e] = heads up to and including (s, e) in plan order, so rank - 1 is the compact row of the statement
     // that (s, e) belongs to -- its own if it is a head, its predecessors' otherwise; the last element (a closing zero flag) counts
     // all heads.  Row 0 of every sub-proof is a head: a group's first compact row is rank[s0][0] - 1.
@@ -85,7 +93,7 @@ static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubP
     HIPCHK(flag.alloc(nf)); HIPCHK(rank.alloc(nf));
     hipLaunchKernelGGL(k_shared_heads, dim3(nblk(nf, 256)), dim3(256), 0, st, P, b, d_idx, flag.p);
     LAUNCH_CHECK();
-    int32_t rc = inclusive_scan_u32(st, flag.p, rank.p, nf);
+    rc = inclusive_scan_u32(st, flag.p, rank.p, nf);
     if (rc) return rc;
     std::vector<uint32_t> g_first(P.n_groups + 1);           // compact row at which each group starts; the last one: all of them
     for (uint32_t gi = 0; gi <= P.n_groups; gi++) {

@@ -436,6 +436,37 @@ class Dapol {
     std::optional<std::vector<DapolProof>> generate_proofs_shared(const std::vector<uint64_t>& leaves, const Bytes32& nonce_seed, int n_bits = 64) const {
         return prove_many(leaves, nonce_seed, n_bits, true);
     }
+    // After update / insert / remove: generate_proofs_shared's proofs for the tree as it is now, proving only the sub-proofs whose
+    // sibling commitments moved (dapol_reprove_entities_shared) and keeping the bytes of the others from old_proofs, which are matched
+    // to `leaves` (strictly increasing) by leaf_index; a leaf without an old proof of this Dapol's shape is proved from scratch, old
+    // proofs of leaves that are gone are ignored.  Returns the proofs and the number of range proofs actually computed.  With old
+    // proofs from generate_proofs_shared under the same nonce_seed the result equals generate_proofs_shared's byte for byte.  Old bytes
+    // are not checked: DapolProof::verify is the check.
+    std::optional<std::pair<std::vector<DapolProof>, uint64_t>> regenerate_proofs_shared(const std::vector<uint64_t>& leaves, const std::vector<DapolProof>& old_proofs,
+                                                                                         const Bytes32& nonce_seed, int n_bits = 64) const {
+        const size_t es = dapol_entity_proof_size(height_, (int)policy_, (int)aggregation_factor_, n_bits);
+        if (es == 0) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        const size_t b = leaves.size(), h = (size_t)height_;
+        std::map<uint64_t, const DapolProof*> by_leaf;
+        for (auto& p : old_proofs)
+            if (p.height == height_ && p.policy == policy_ && p.aggregation_factor == aggregation_factor_ && p.n_bits == n_bits && p.merkle_siblings.size() == h &&
+                p.range_proofs.size() == es)
+                by_leaf[p.leaf_index] = &p;
+        std::vector<uint8_t> has_old(b + 1, 0), oldC(b * h * 32 + 1, 0), oldR(b * es + 1, 0), C(b * h * 32 + 1), H(b * h * 32 + 1), R(b * es + 1);
+        for (size_t e = 0; e < b; e++) {
+            auto it = by_leaf.find(leaves[e]);
+            if (it == by_leaf.end()) continue;
+            has_old[e] = 1;
+            for (size_t s = 0; s < h; s++) std::memcpy(&oldC[(e * h + s) * 32], it->second->merkle_siblings[s].com.data(), 32);
+            std::memcpy(&oldR[e * es], it->second->range_proofs.data(), es);
+        }
+        uint64_t proved = 0;
+        int32_t rc = dapol_reprove_entities_shared(ctx_->get(), tree_.get(), b, leaves.data(), (int)policy_, (int)aggregation_factor_, n_bits, nonce_seed.data(),
+                                                   has_old.data(), oldC.data(), oldR.data(), C.data(), H.data(), R.data(), &proved, nullptr);
+        if (rc == DAPOL_ERR_UNKNOWN_LEAF) return std::nullopt;
+        check(rc);
+        return std::make_pair(unpack(leaves, C, H, R, es, n_bits), proved);
+    }
     // Verifies many single-leaf proofs in one call with every run of equal sub-proofs checked once (dapol_verify_entities_shared):
     // a verdict per proof -- the ones DapolProof::verify gives one by one -- and the number of range proofs actually checked.  Proofs
     // of generate_proofs_shared in their order share the most; any proofs of one (height, policy, aggregation factor, n_bits) may
@@ -490,6 +521,12 @@ class Dapol {
                                                    nonce_seed.data(), C.data(), H.data(), R.data());
         if (rc == DAPOL_ERR_UNKNOWN_LEAF) return std::nullopt;
         check(rc);
+        return unpack(leaves, C, H, R, es, n_bits);
+    }
+    // [b][h][32] siblings + [b][es] blobs -> one DapolProof per leaf
+    std::vector<DapolProof> unpack(const std::vector<uint64_t>& leaves, const std::vector<uint8_t>& C, const std::vector<uint8_t>& H, const std::vector<uint8_t>& R,
+                                   size_t es, int n_bits) const {
+        const size_t b = leaves.size(), h = (size_t)height_;
         std::vector<DapolProof> out(b);
         for (size_t e = 0; e < b; e++) {
             out[e].leaf_index = leaves[e];

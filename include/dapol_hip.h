@@ -331,6 +331,50 @@ int32_t dapol_prove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b, 
                                     const uint8_t* up_C32, const uint8_t* up_H32, const uint64_t* up_v, const uint8_t* up_r32,
                                     uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out, uint64_t* unique_subproofs_out);
 
+/* RE-PROVING after an edit of the tree (dapol_tree_update / _insert / _remove): a sub-proof {start, count, m} is a statement about
+ * `count` sibling commitments, a sibling changes only when an edited leaf lies below it, and the shared prover's nonce key is bound
+ * to the seed, S, (n, m) and those commitments -- so an unchanged statement has unchanged bytes and a changed one gets fresh nonces.
+ * dapol_reprove_entities_shared takes the caller's old paths and blobs and proves only what moved.  The plan, S and the sibling
+ * order are dapol_prove_entities_shared's.  PLAIN TREES ONLY: there is no n_upper, the sharded form is out of scope (DESIGN.md
+ * section 9); a 64-byte-digest context works as in dapol_prove_entities_shared.
+ *   Arguments.  leaf_idx: strictly increasing, the leaves of the tree AS IT IS NOW.  old_path_C32 [b][H][32] (the paths the old blobs
+ * were proved over) and old_range [b][dapol_entity_proof_size] are ALIGNED with leaf_idx: the caller drops the rows of removed
+ * leaves and sets has_old[e] = 0 for newly inserted ones, whose old rows are ignored.  has_old = NULL: every row has old data.
+ *   Definitions.  DIRTY(s, e): has_old[e] == 0, or the `count` commitments old_path_C32[e][start .. start + count) differ from the
+ * tree's current ones -- a comparison of bytes: nothing is keyed, no index is trusted.  The siblingless pad proof of aggregation 0
+ * (count = 0) is dirty only without an old row.  HEAD(s, e): DIRTY(s, e) and (e = 0, or the key S of row e differs from row e - 1's,
+ * or row e - 1 is not dirty).  Every head is proved once, with stream id S and slot base 0: exactly the bytes
+ * dapol_prove_entities_shared gives that statement.  A dirty non-head row takes the proof of the head before it; a row that is not
+ * dirty keeps its old bytes.  *proved_out = heads, *kept_out = kept (s, e) pairs (both may be NULL).  A kept row in the middle of a
+ * key run may split the run into two heads: both give the same bytes, so this costs only work.
+ *   Consequences.  If the old data came from dapol_prove_entities_shared under the same seed, policy, factor and n_bits, the outputs
+ * equal a fresh dapol_prove_entities_shared on the edited tree byte for byte.  With another seed the kept proofs stay valid but
+ * differ from a fresh call.  Old bytes are NOT checked: what goes in on a kept row comes out unchanged -- dapol_verify_entities is
+ * the check.  Outputs may alias the old arrays (every input is uploaded before anything is written back).  Refusals as
+ * dapol_prove_entities_shared: an unknown leaf (DAPOL_ERR_UNKNOWN_LEAF) or non-increasing indexes write nothing; in addition a NULL
+ * old array while some has_old is set (or implied by has_old = NULL) is DAPOL_ERR_INVALID_ARGUMENT.  b = 0 is DAPOL_OK.
+ *   dapol_reprove_plan: host-only index arithmetic (no GPU, no tree) with the same HEAD rule.  edited_idx: strictly increasing, the
+ * replaced, inserted and removed leaves.  DIRTY(s, e): !has_old[e], or some edited x != leaf e first differs from leaf e at a depth
+ * that one of the sub-proof's siblings occupies (depth counted from the root: sibling i lies at depth i + 1, or H - i leaf first).
+ * An entity's own edit dirties nothing of its own.  Exact when every edit really changes its leaf's commitment, an upper bound
+ * otherwise.  n_proved_out[s] (may be NULL) = heads of sub-proof s, *total_proved their sum = what dapol_reprove_entities_shared
+ * proves, *sum_m_proved = the sum of m over them, *sum_m_shared = the sum of m over dapol_shared_plan's statements: one call gives
+ * the ratio.  Refusals as dapol_shared_plan (for edited_idx as for leaf_idx).
+ *   When to use it (tools/bench_reprove.py): the time follows the sum of m over the heads plus the trip of the
+ * old arrays to the device.  2^20 random leaves at height 32, 64-bit proofs, one MI355X, whole call against dapol_prove_entities_shared
+ * on the same edited tree: padding / 16 9.33 -> 1.13-1.16 s (x8.0-8.2; the sum-of-m ratio is 13.8-14.0) and splitting / 24 10.67 ->
+ * 0.97-1.29 s (x8.3-11.0 of 11.4-16.7) for 1, 64 and 4,096 replaced liabilities; padding / 0 9.13 -> 1.24 s (x7.3: 0.80 s of it is the
+ * upload of the 24 GB of old blobs); padding / 32 18.744 -> 18.828 s, +0.45 % where the shared call's spread is 0.04 %.  Where
+ * dapol_reprove_plan reports nothing to keep (padding with aggregation_factor = H: the one sub-proof covers every sibling, and an edit lies below one
+ * sibling of every other leaf) the call can only add the upload and the comparison to the shared call: use the shared call there. */
+int32_t dapol_reprove_plan(int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* has_old, size_t k, const uint64_t* edited_idx,
+                           int32_t policy, int32_t aggregation_factor, uint64_t* n_proved_out, uint64_t* total_proved, uint64_t* sum_m_proved,
+                           uint64_t* sum_m_shared);
+int32_t dapol_reprove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b, const uint64_t* leaf_idx, int32_t policy,
+                                      int32_t aggregation_factor, int32_t n_bits, const uint8_t nonce_seed32[32], const uint8_t* has_old,
+                                      const uint8_t* old_path_C32, const uint8_t* old_range, uint8_t* path_C32, uint8_t* path_H32,
+                                      uint8_t* range_out, uint64_t* proved_out, uint64_t* kept_out);
+
 /* Serializable for RangeProofPadding / RangeProofSplitting (src/range/padding.rs:38-69, src/range/splitting.rs:36-84):
  * the range-proof blob of ONE entity as written by dapol_prove_entities <-> R::serialize() bytes
  * ((aggregated_num ||) (size || proof)... || individual_num || proofs...; field widths src/range/mod.rs:18-21).
