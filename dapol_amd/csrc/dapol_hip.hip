@@ -121,7 +121,7 @@ struct dapol_ctx {
     RangeScratch scratch;        // grown on demand by the range prover
     RangeScratch vio;            // dapol_range_verify_batch's device copies of the caller's proofs / commitments / verdicts: kept between calls
                                  // (a 34 MB hipMalloc + hipFree per call is a few hundred microseconds of a 7 ms pass; at most 1 GB is kept)
-    // LANES for the sub-proofs of ONE small call (round 6, host_range.inc: prove_policy_device): a policy's plan with several groups
+    // LANES for the sub-proofs of ONE small call (round 6, host_policy.inc: prove_policy_device): a policy's plan with several groups
     // of sub-proofs -- splitting at height 24 is a 16-party and an 8-party proof, benches/dapol.rs:71-78 -- is latency-bound, and its
     // groups are independent statements; each extra group runs on a lane of its own: a shallow context that shares the tables (tv)
     // and owns its streams, events and scratch.  Made on first use, freed with the context.
@@ -447,8 +447,12 @@ int32_t dapol_commit_hash_batch(dapol_ctx* ctx, size_t n, const uint64_t* v, con
 #include "host_tree.inc"
 #include "host_tree_edit.inc"
 #include "host_range.inc"
+#include "host_policy.inc"
+#include "host_entity.inc"
+#include "host_workload.inc"
 #include "host_shared.inc"
 #include "host_reprove.inc"
+#include "host_verify.inc"
 #include "host_verify_shared.inc"
 #include "host_leaf.inc"
 #include "host_wire.inc"

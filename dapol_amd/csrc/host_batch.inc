@@ -5,7 +5,7 @@
 // Sibling order (smtree's own order is not pinned by anything in the reference repository -- DESIGN.md section 2):
 // level by level from the root side (dapol_wire_config.siblings_leaf_first = 1: from the leaf level up), left to right within a
 // level.  For k = 1 this is dapol_tree_paths' order.
-// Included at the end of dapol_hip.hip.
+// Included from dapol_hip.hip after the prover's and the verifier's files.
 
 struct BatchSib { int level; uint64_t index; uint32_t src_leaf; };      // level 0 = leaves; src_leaf: a leaf below the sibling's sibling
 
@@ -73,6 +73,34 @@ __global__ void k_batch_gather(size_t n, const uint32_t* src, PathOut in, PathOu
     out.v[i] = in.v[s];
 }
 
+// What a batch asks of its policy: the plan over its S siblings, the words of its blob and (max_m != null) its widest sub-proof.
+static int32_t batch_policy_plan(const dapol_ctx* ctx, size_t S, int policy, int agg, int n_bits, std::vector<SubProof>& plan, size_t& words, int* max_m = nullptr) {
+    if (!policy_plan(policy, (int)S, agg, plan)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation_factor must be within [0, number of siblings]");
+    if (dapol_range_proof_size(n_bits, 1) == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "n_bits must be 8/16/32/64");
+    words = 0;
+    for (auto& s : plan) {
+        if (s.m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
+        if (max_m && s.m > *max_m) *max_m = s.m;
+        words += dapol_range_proof_size(n_bits, s.m) / 4;
+    }
+    return DAPOL_OK;
+}
+// The tail of both batch provers: the batch's own seed (k > 1), R::generate_proof over the S siblings in HBM, the blob back.
+static int32_t batch_prove_tail(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t k, const uint64_t* d_leaf, size_t S, const uint64_t* sv, const uint32_t* sr,
+                                const uint32_t* sC, int n_bits, const uint32_t* d_seed, size_t words, uint8_t* range_out) {
+    DevBuf<uint32_t> bseed, dout;
+    HIPCHK(bseed.alloc(8)); HIPCHK(dout.alloc(words));
+    if (k > 1) {
+        hipLaunchKernelGGL(k_batch_seed, dim3(1), dim3(64), 0, ctx->stream, d_seed, k, d_leaf, bseed.p);
+        LAUNCH_CHECK();
+        d_seed = bseed.p;
+    }
+    int32_t rc = prove_policy_device(ctx, plan, 1, (int)S, sv, sr, sC, n_bits, d_seed, d_leaf, dout.p, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(range_out, dout.p, words * 4, hipMemcpyDeviceToHost));
+    return DAPOL_OK;
+}
+
 int32_t dapol_prove_batch(dapol_ctx* ctx, dapol_tree* tree, size_t k, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor,
                           int32_t n_bits, const uint8_t nonce_seed32[32], uint8_t* sib_C32, uint8_t* sib_H32, uint8_t* range_out) {
     WIRE_SCOPE();
@@ -85,22 +113,16 @@ int32_t dapol_prove_batch(dapol_ctx* ctx, dapol_tree* tree, size_t k, const uint
     const size_t S = sibs.size();
     if (S > (size_t)1 << 20) return fail(DAPOL_ERR_INVALID_ARGUMENT, "batch too large");
     std::vector<SubProof> plan;
-    if (!policy_plan(policy, (int)S, aggregation_factor, plan)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation_factor must be within [0, number of siblings]");
-    if (dapol_range_proof_size(n_bits, 1) == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "n_bits must be 8/16/32/64");
     size_t words = 0;
-    for (auto& s : plan) {
-        if (s.m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
-        words += dapol_range_proof_size(n_bits, s.m) / 4;
-    }
+    if (int32_t rc = batch_policy_plan(ctx, S, policy, aggregation_factor, n_bits, plan, words)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t tot = k * (size_t)H, hw = (size_t)ctx_hw(ctx);
     DevBuf<uint64_t> dl, pv, sv;
-    DevBuf<uint32_t> dseed, bseed, pC, pH, pr, pos, sC, sH, sr, dsrc, dout;
-    HIPCHK(dl.alloc(k)); HIPCHK(dseed.alloc(8)); HIPCHK(bseed.alloc(8)); HIPCHK(pos.alloc(k));
+    DevBuf<uint32_t> dseed, pC, pH, pr, pos, sC, sH, sr, dsrc;
+    HIPCHK(dl.alloc(k)); HIPCHK(dseed.alloc(8)); HIPCHK(pos.alloc(k));
     HIPCHK(pC.alloc(tot * 8 + 8)); HIPCHK(pH.alloc(tot * hw + 16)); HIPCHK(pr.alloc(tot * 8 + 8)); HIPCHK(pv.alloc(tot + 1));
     HIPCHK(sC.alloc(S * 8 + 8)); HIPCHK(sH.alloc(S * hw + 16)); HIPCHK(sr.alloc(S * 8 + 8)); HIPCHK(sv.alloc(S + 1)); HIPCHK(dsrc.alloc(S + 1));
-    HIPCHK(dout.alloc(words));
     HIPCHK(hipMemcpyAsync(dl.p, leaf_idx, k * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dseed.p, nonce_seed32, 32, hipMemcpyHostToDevice, st));
     PathOut po{pC.p, pH.p, pv.p, pr.p};
@@ -114,17 +136,10 @@ int32_t dapol_prove_batch(dapol_ctx* ctx, dapol_tree* tree, size_t k, const uint
         hipLaunchKernelGGL(k_batch_gather, dim3(nblk(S, 256)), dim3(256), 0, st, S, dsrc.p, po, so, (int)hw);
         LAUNCH_CHECK();
     }
-    const uint32_t* seed = dseed.p;
-    if (k > 1) {
-        hipLaunchKernelGGL(k_batch_seed, dim3(1), dim3(64), 0, st, dseed.p, k, dl.p, bseed.p);
-        LAUNCH_CHECK();
-        seed = bseed.p;
-    }
-    rc = prove_policy_device(ctx, plan, 1, (int)S, sv.p, sr.p, sC.p, n_bits, seed, dl.p, dout.p, nullptr);
+    rc = batch_prove_tail(ctx, plan, k, dl.p, S, sv.p, sr.p, sC.p, n_bits, dseed.p, words, range_out);
     if (rc) return rc;
     if (sib_C32 && S) HIPCHK(hipMemcpy(sib_C32, sC.p, S * 32, hipMemcpyDeviceToHost));
     if (sib_H32 && S) HIPCHK(hipMemcpy(sib_H32, sH.p, S * hw * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(range_out, dout.p, words * 4, hipMemcpyDeviceToHost));
     return DAPOL_OK;
 }
 
@@ -165,15 +180,9 @@ int32_t dapol_verify_batch(dapol_ctx* ctx, int32_t height, size_t k, const uint6
     const size_t S = sibs.size();
     if (S != n_siblings) return DAPOL_OK;                                 // wrong number of siblings for these leaves: proof rejected
     std::vector<SubProof> plan;
-    if (!policy_plan(policy, (int)S, aggregation_factor, plan)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation_factor must be within [0, number of siblings]");
-    if (dapol_range_proof_size(n_bits, 1) == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "n_bits must be 8/16/32/64");
     size_t words = 0;
     int max_m = 1;
-    for (auto& s : plan) {
-        if (s.m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
-        if (s.m > max_m) max_m = s.m;
-        words += dapol_range_proof_size(n_bits, s.m) / 4;
-    }
+    if (int32_t rc = batch_policy_plan(ctx, S, policy, aggregation_factor, n_bits, plan, words, &max_m)) return rc;
     // merge schedule: walk the levels bottom-up; sibling slots are consumed in plan order within their level
     std::vector<size_t> level_first((size_t)height + 1, 0);               // first plan entry of each level
     for (size_t i = S; i-- > 0;) level_first[sibs[i].level] = i;        // (a level's siblings are contiguous in either sibling order)
@@ -332,19 +341,13 @@ int32_t dapol_prove_batch_records(dapol_ctx* ctx, size_t k, const uint64_t* leaf
     const size_t S = n_siblings;
     if (S > (size_t)1 << 20) return fail(DAPOL_ERR_INVALID_ARGUMENT, "batch too large");
     std::vector<SubProof> plan;
-    if (!policy_plan(policy, (int)S, aggregation_factor, plan)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation_factor must be within [0, number of siblings]");
-    if (dapol_range_proof_size(n_bits, 1) == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "n_bits must be 8/16/32/64");
     size_t words = 0;
-    for (auto& s : plan) {
-        if (s.m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
-        words += dapol_range_proof_size(n_bits, s.m) / 4;
-    }
+    if (int32_t rc = batch_policy_plan(ctx, S, policy, aggregation_factor, n_bits, plan, words)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevBuf<uint64_t> dl, sv;
-    DevBuf<uint32_t> dseed, bseed, sC, sr, dout;
-    HIPCHK(dl.alloc(k)); HIPCHK(dseed.alloc(8)); HIPCHK(bseed.alloc(8)); HIPCHK(sC.alloc(S * 8 + 8)); HIPCHK(sr.alloc(S * 8 + 8)); HIPCHK(sv.alloc(S + 1));
-    HIPCHK(dout.alloc(words));
+    DevBuf<uint32_t> dseed, sC, sr;
+    HIPCHK(dl.alloc(k)); HIPCHK(dseed.alloc(8)); HIPCHK(sC.alloc(S * 8 + 8)); HIPCHK(sr.alloc(S * 8 + 8)); HIPCHK(sv.alloc(S + 1));
     HIPCHK(hipMemcpyAsync(dl.p, leaf_idx, k * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dseed.p, nonce_seed32, 32, hipMemcpyHostToDevice, st));
     if (S) {
@@ -352,16 +355,7 @@ int32_t dapol_prove_batch_records(dapol_ctx* ctx, size_t k, const uint64_t* leaf
         HIPCHK(hipMemcpyAsync(sr.p, sib_r32, S * 32, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(sv.p, sib_v, S * 8, hipMemcpyHostToDevice, st));
     }
-    const uint32_t* seed = dseed.p;
-    if (k > 1) {
-        hipLaunchKernelGGL(k_batch_seed, dim3(1), dim3(64), 0, st, dseed.p, k, dl.p, bseed.p);
-        LAUNCH_CHECK();
-        seed = bseed.p;
-    }
-    int32_t rc = prove_policy_device(ctx, plan, 1, (int)S, sv.p, sr.p, sC.p, n_bits, seed, dl.p, dout.p, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(range_out, dout.p, words * 4, hipMemcpyDeviceToHost));
-    return DAPOL_OK;
+    return batch_prove_tail(ctx, plan, k, dl.p, S, sv.p, sr.p, sC.p, n_bits, dseed.p, words, range_out);
 }
 
 // Length-checked forms of the two verifier entry points, for callers whose buffers come from UNTRUSTED bytes (a decoded wire):

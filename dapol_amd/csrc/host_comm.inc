@@ -2,7 +2,7 @@
 // any language gets it through the C ABI: ONE ncclAllGather of the G subtree-root records (104 bytes each, latency-bound
 // over xGMI), the replicated merge of the top log2 G levels on every rank's own GPU, and ncclAllReduce for the final
 // reduce of the proof checksums / verdict counts.  The reference has no communication at all (single process, single
-// thread); there is nothing to translate.  Included at the end of dapol_hip.hip.
+// thread); there is nothing to translate.  Included from dapol_hip.hip, last.
 #include <rccl/rccl.h>
 #include <chrono>
 #include <thread>

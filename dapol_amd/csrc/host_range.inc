@@ -1,5 +1,5 @@
-// Host orchestration of the batched range prover, the per-entity inclusion proofs and the bench workload.
-// Included at the end of dapol_hip.hip.
+// Host orchestration of the batched range prover: the plan of a call (prove_plan.inc) turned into launches.
+// Included from dapol_hip.hip; the policy layer on top of it is host_policy.inc.
 
 #include <cstdlib>
 #include "policy_plan.inc"
@@ -459,463 +459,3 @@ int32_t dapol_range_prove_batch(dapol_ctx* ctx, int32_t n_bits, int32_t m, size_
     { float ms = 0; if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) g_last_range_prove_ms.store((double)ms, std::memory_order_relaxed); }
     return DAPOL_OK;
 }
-
-// parties of the sub-proofs of one group from the gathered paths: proof g = e * k + j (entity e, sub-proof j of the group) takes
-// the siblings start + j * m ... of its entity; pad parties are (0, Scalar::one()) with commitment B_blinding
-__global__ void k_gather_parties(size_t b, int height, int start, int count, int m, int k, const uint64_t* pv, const uint32_t* pr,
-                                 const uint32_t* pC, const uint32_t* Bb_comp, uint64_t* vals, uint32_t* blind, uint32_t* Vc) {
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= b * (size_t)k * (size_t)m) return;
-    const size_t g = t / m, e = g / k;
-    const int jj = (int)(t - g * m), j = (int)(g - e * k);
-    uint32_t r[8] = {1, 0, 0, 0, 0, 0, 0, 0}, c[8];
-    uint64_t v = 0;
-    if (jj < count) {
-        size_t s = e * (size_t)height + (size_t)(start + j * m + jj);
-        v = pv[s];
-        ld8(r, pr + s * 8);
-        ld8(c, pC + s * 8);
-    } else {
-        for (int i = 0; i < 8; i++) c[i] = Bb_comp[i];
-    }
-    vals[t] = v;
-    st8(blind + t * 8, r);
-    st8(Vc + t * 8, c);
-}
-
-static bool policy_grouping_on() { return !knob("DAPOL_NO_GROUP"); }      // prover and verifier alike (policy_plan.inc: group_policy_plan)
-// R::generate_proof (src/range/padding.rs:88-118, splitting.rs:100-129) for b proofs over H siblings each: pv / pr / pC
-// are [b][H] device arrays of the siblings' values, blindings and commitments; one RNG stream (d_stream[e]) per proof
-// runs across its sub-proofs.  d_range: [b][sum of the plan's proof words].
-// A run of the plan's sub-proofs of EQUAL size (the individual proofs of the siblings beyond aggregation_factor -- padding.rs:104-112,
-// splitting.rs:118-123 -- with the one-party part of an odd split before them) is ONE call of b * k proofs (RangeArgs::sub_k): same
-// draws, same bytes, one pipeline of full launches instead of k part-filled ones (round 6; DAPOL_NO_GROUP=1 proves them one by one).
-static int32_t prove_policy_device(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t b, int H, const uint64_t* pv, const uint32_t* pr,
-                                   const uint32_t* pC, int n_bits, const uint32_t* d_seed, const uint64_t* d_stream, uint32_t* d_range,
-                                   MsmTiming* tm, const uint32_t* d_tape = nullptr /* [b][tape_slots][16]: tape mode */, size_t tape_slots = 0) {
-    hipStream_t st = ctx->stream;
-    size_t entity_words = 0;
-    for (auto& s : plan) entity_words += dapol_range_proof_size(n_bits, s.m) / 4;
-    const PolicyGroups PG = group_policy_plan(plan, policy_grouping_on());
-    const std::vector<PolicyGroup>& groups = PG.groups;
-    const size_t max_parties = PG.max_parties, sum_parties = PG.sum_parties, sum_proofs = PG.sum_proofs;
-    const uint32_t* Bb_comp = ctx->gens_comp.p + (size_t)ctx->tv.row_Bb(0) * 8;
-    // A SMALL call whose plan has several groups (splitting at aggregation 24 = a 16-party and an 8-party proof: one of the reference's
-    // six `prove` cases, benches/dapol.rs:71-78; any plan with individual proofs) is a chain of latencies per group, and the groups are
-    // independent statements: each runs on a lane of its own (dapol_ctx::aux -- own streams, events and scratch, the same tables),
-    // queued without a host wait, and the call waits for all of them at the end.  Same bytes (the groups' draws and outputs are
-    // disjoint).  DAPOL_NO_LANES=1: one after the other.  It pays well beyond the latency regime -- while one group's kernels cannot
-    // fill the chip, another's run beside them: padding at aggregation 24, one call of 1 / 16 / 256 / 1,024 / 4,096 entities 9.5 / 11.8 /
-    // 22.9 / 42.0 / 117.4 ms one after the other, 6.2 / 8.8 / 17.6 / 38.0 / 110.1 ms on lanes; 8,192: -3 %, 16,384: -1 %
-    // (profiles/r6_lanes_midsize.txt) -- so up to 40,000 sub-proofs per call.
-    size_t lanes_max = 40000;                                // most sub-proofs of a call whose groups take lanes (DAPOL_LANES_MAX)
-    if (const char* e = knob("DAPOL_LANES_MAX")) { long long v = atoll(e); if (v >= 2) lanes_max = (size_t)v; }
-    if (groups.size() >= 2 && groups.size() <= 64 && b * sum_proofs <= lanes_max && !tm && !knob("DAPOL_NO_LANES")) {
-        DevBuf<uint64_t> vals;
-        DevBuf<uint32_t> blind, Vc;
-        HIPCHK(vals.alloc(b * sum_parties)); HIPCHK(blind.alloc(b * sum_parties * 8)); HIPCHK(Vc.alloc(b * sum_parties * 8));
-        std::vector<PendingProve> pend(groups.size());       // (sized once: the queued copies of the flags point into it)
-        size_t word_off = 0, party_off = 0;
-        uint64_t slot_base = 0;
-        std::vector<size_t> p_off(groups.size()), w_off(groups.size());
-        std::vector<uint64_t> s_base(groups.size());
-        for (size_t gi = 0; gi < groups.size(); gi++) {      // every group's parties, on the context's stream
-            auto& g = groups[gi];
-            p_off[gi] = party_off; w_off[gi] = word_off; s_base[gi] = slot_base;
-            hipLaunchKernelGGL(k_gather_parties, dim3(nblk(b * (size_t)g.k * (size_t)g.m, 256)), dim3(256), 0, st, b, H, g.start, g.count, g.m, g.k, pv, pr, pC,
-                               Bb_comp, vals.p + party_off, blind.p + party_off * 8, Vc.p + party_off * 8);
-            LAUNCH_CHECK();
-            party_off += b * (size_t)g.k * (size_t)g.m;
-            word_off += dapol_range_proof_size(n_bits, g.m) / 4 * (size_t)g.k;
-            slot_base += (uint64_t)g.k * (uint64_t)g.m * (2 * (uint64_t)n_bits + 4);
-        }
-        HIPCHK(hipEventRecord(ctx->ev_v[0], st));            // (an event of the context that no prover path uses)
-        int32_t rc = DAPOL_OK;
-        for (size_t gi = 0; gi < groups.size() && !rc; gi++) {
-            auto& g = groups[gi];
-            dapol_ctx* lane = nullptr;
-            rc = ctx_lane(ctx, (int)(gi % 4), &lane);
-            if (rc) break;
-            if (lane != ctx) HIPCHK(hipStreamWaitEvent(lane->stream, ctx->ev_v[0], 0));
-            const uint32_t* sub_tape = d_tape ? d_tape + s_base[gi] * 16 : nullptr;
-            pend[gi].pinned_slot = (int)((gi / 4) % 16);
-            rc = range_prove_device(lane, n_bits, g.m, b * (size_t)g.k, vals.p + p_off[gi], blind.p + p_off[gi] * 8, Vc.p + p_off[gi] * 8, d_seed, d_stream, s_base[gi],
-                                    sub_tape, d_range + w_off[gi], nullptr, tape_slots, (uint32_t)g.k, entity_words, &pend[gi]);
-        }
-        for (auto& pnd : pend) { int32_t r2 = pnd.finish(); if (!rc) rc = r2; }     // (every lane drains before the inputs are freed)
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(st));
-        return DAPOL_OK;
-    }
-    DevBuf<uint64_t> vals;
-    DevBuf<uint32_t> blind, Vc;
-    HIPCHK(vals.alloc(b * max_parties)); HIPCHK(blind.alloc(b * max_parties * 8)); HIPCHK(Vc.alloc(b * max_parties * 8));
-    size_t word_off = 0;
-    uint64_t slot_base = 0;
-    for (auto& g : groups) {
-        const size_t pw = dapol_range_proof_size(n_bits, g.m) / 4;
-        hipLaunchKernelGGL(k_gather_parties, dim3(nblk(b * (size_t)g.k * (size_t)g.m, 256)), dim3(256), 0, st, b, H, g.start, g.count, g.m, g.k, pv, pr, pC,
-                           Bb_comp, vals.p, blind.p, Vc.p);
-        LAUNCH_CHECK();
-        const uint32_t* sub_tape = d_tape ? d_tape + slot_base * 16 : nullptr;     // the group's first slot inside every entity's row
-        int32_t rc = range_prove_device(ctx, n_bits, g.m, b * (size_t)g.k, vals.p, blind.p, Vc.p, d_seed, d_stream, slot_base, sub_tape, d_range + word_off, tm,
-                                        tape_slots, (uint32_t)g.k, entity_words);
-        if (rc) return rc;
-        word_off += pw * (size_t)g.k;
-        slot_base += (uint64_t)g.k * (uint64_t)g.m * (2 * (uint64_t)n_bits + 4);      // one RNG stream across the sub-proofs
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    return DAPOL_OK;
-}
-
-// Device-side core of Dapol::generate_proof for b single leaves (leaf indexes already in HBM).
-// d_range: [b][entity_words]; d_pathC/H may be null.
-struct UpperSibs {           // device arrays of the n siblings above a shard root, root side first (n may be 0)
-    int n = 0;
-    const uint32_t* C = nullptr;
-    const uint32_t* H = nullptr;
-    const uint64_t* v = nullptr;
-    const uint32_t* r = nullptr;
-};
-static int32_t prove_entities_device(dapol_ctx* ctx, dapol_tree* tree, size_t b, const uint64_t* d_leaf_idx, int policy, int agg,
-                                     int n_bits, const uint32_t* d_seed, UpperSibs up, uint32_t* d_pathC, uint32_t* d_pathH,
-                                     uint32_t* d_range, MsmTiming* tm, const uint32_t* d_tape = nullptr, size_t tape_slots = 0) {
-    hipStream_t st = ctx->stream;
-    const int H = tree->height + up.n;
-    std::vector<SubProof> plan;
-    if (!policy_plan(policy, H, agg, plan)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation_factor must be within [0, tree height]");
-    size_t entity_words = 0;
-    int max_m = 1;
-    for (auto& s : plan) { entity_words += dapol_range_proof_size(n_bits, s.m) / 4; if (s.m > max_m) max_m = s.m; }
-    if (dapol_range_proof_size(n_bits, 1) == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "n_bits must be 8/16/32/64");
-    if (max_m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
-    const size_t tot = b * (size_t)H;
-    DevBuf<uint64_t> pv;
-    DevBuf<uint32_t> pr, pCtmp, pos;
-    HIPCHK(pv.alloc(tot)); HIPCHK(pr.alloc(tot * 8)); HIPCHK(pos.alloc(b));
-    uint32_t* pathC = d_pathC;
-    if (!pathC) { HIPCHK(pCtmp.alloc(tot * 8)); pathC = pCtmp.p; }
-    PathOut po{pathC, d_pathH, pv.p, pr.p};
-    int32_t rc = tree_paths_device(tree, b, d_leaf_idx, po, pos.p, up.n);
-    if (rc) return rc;
-    if (up.n) {
-        hipLaunchKernelGGL(k_tree_path_upper, dim3(nblk(b * (size_t)up.n, 256)), dim3(256), 0, st, b, tree->height, up.n, g_wire.siblings_leaf_first, up.C,
-                           up.H, up.v, up.r, po);
-        LAUNCH_CHECK();
-    }
-    return prove_policy_device(ctx, plan, b, H, pv.p, pr.p, pathC, n_bits, d_seed, d_leaf_idx, d_range, tm, d_tape, tape_slots);
-}
-
-struct UpperDev {             // uploads host upper-sibling arrays
-    DevBuf<uint32_t> C, H, r;
-    DevBuf<uint64_t> v;
-    UpperSibs view;
-    int32_t upload(hipStream_t st, int n, const uint8_t* C32, const uint8_t* H32, const uint64_t* v64, const uint8_t* r32) {
-        view = UpperSibs{};
-        if (n <= 0) return DAPOL_OK;
-        if (!C32 || !H32 || !v64 || !r32) return fail(DAPOL_ERR_INVALID_ARGUMENT, "upper sibling arrays missing");
-        HIPCHK(C.alloc((size_t)n * 8)); HIPCHK(H.alloc((size_t)n * 8)); HIPCHK(r.alloc((size_t)n * 8)); HIPCHK(v.alloc((size_t)n));
-        HIPCHK(hipMemcpyAsync(C.p, C32, (size_t)n * 32, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(H.p, H32, (size_t)n * 32, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(r.p, r32, (size_t)n * 32, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(v.p, v64, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        view.n = n; view.C = C.p; view.H = H.p; view.v = v.p; view.r = r.p;
-        return DAPOL_OK;
-    }
-};
-
-int32_t dapol_prove_entities_upper(dapol_ctx* ctx, dapol_tree* tree, size_t b, const uint64_t* leaf_idx, int32_t policy,
-                                   int32_t aggregation_factor, int32_t n_bits, const uint8_t nonce_seed32[32], int32_t n_upper,
-                                   const uint8_t* up_C32, const uint8_t* up_H32, const uint64_t* up_v, const uint8_t* up_r32,
-                                   uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out) {
-    WIRE_SCOPE();
-    if (!ctx || !tree || tree->ctx != ctx || !nonce_seed32 || (b && (!leaf_idx || !range_out)) || n_upper < 0 || n_upper > 16)
-        return fail(DAPOL_ERR_INVALID_ARGUMENT, "null or out-of-range argument");
-    if (n_upper) NEEDS_32_BYTE_DIGEST(ctx, "the sharded (multi-GPU) path");
-    const int Htot = tree->height + n_upper;
-    size_t es = dapol_entity_proof_size(Htot, policy, aggregation_factor, n_bits);
-    if (es == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation_factor / n_bits");
-    if (b == 0) return DAPOL_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t tot = b * (size_t)Htot;
-    DevBuf<uint64_t> dl;
-    DevBuf<uint32_t> dseed, dC, dH, dout;
-    UpperDev up;
-    HIPCHK(dl.alloc(b)); HIPCHK(dseed.alloc(8)); HIPCHK(dC.alloc(tot * 8)); HIPCHK(dH.alloc(tot * (size_t)ctx_hw(ctx))); HIPCHK(dout.alloc(b * es / 4));
-    HIPCHK(hipMemcpyAsync(dl.p, leaf_idx, b * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dseed.p, nonce_seed32, 32, hipMemcpyHostToDevice, st));
-    int32_t rc = up.upload(st, n_upper, up_C32, up_H32, up_v, up_r32);
-    if (rc) return rc;
-    rc = prove_entities_device(ctx, tree, b, dl.p, policy, aggregation_factor, n_bits, dseed.p, up.view, dC.p, dH.p, dout.p, nullptr);
-    if (rc) return rc;
-    if (path_C32) HIPCHK(hipMemcpy(path_C32, dC.p, tot * 32, hipMemcpyDeviceToHost));
-    if (path_H32) HIPCHK(hipMemcpy(path_H32, dH.p, tot * ctx_hash_bytes(ctx), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(range_out, dout.p, b * es, hipMemcpyDeviceToHost));
-    return DAPOL_OK;
-}
-// Wide draws one entity's range proofs consume, in the crate's draw order: the sub-proofs of the policy one after the other (one RNG
-// runs through R::generate_proof, src/range/padding.rs:104-112 / splitting.rs:110-123), each m (2 n_bits + 4) draws.
-size_t dapol_entity_tape_slots(int32_t height, int32_t policy, int32_t aggregation_factor, int32_t n_bits) {
-    std::vector<SubProof> plan;
-    if (height < 0 || height > 80 || !policy_plan(policy, height, aggregation_factor, plan) || dapol_range_proof_size(n_bits, 1) == 0) return 0;
-    size_t slots = 0;
-    for (auto& s : plan) slots += (size_t)s.m * (2 * (size_t)n_bits + 4);
-    return slots;
-}
-// dapol_prove_entities in TAPE mode: every nonce of entity e is read from tape[e][slot][64] (64 bytes reduced mod l, Scalar::random)
-// instead of being derived from a seed -- what a Rust harness replays through a custom RngCore into prove_multiple_with_rng.
-int32_t dapol_prove_entities_tape(dapol_ctx* ctx, dapol_tree* tree, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor,
-                                  int32_t n_bits, const uint8_t* tape, uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out) {
-    WIRE_SCOPE();
-    if (!ctx || !tree || tree->ctx != ctx || (b && (!leaf_idx || !range_out || !tape))) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    const int H = tree->height;
-    const size_t es = dapol_entity_proof_size(H, policy, aggregation_factor, n_bits), slots = dapol_entity_tape_slots(H, policy, aggregation_factor, n_bits);
-    if (es == 0 || slots == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation_factor / n_bits");
-    if (tree->shard_bits) return fail(DAPOL_ERR_INVALID_ARGUMENT, "tape mode proves over a whole tree (not a shard)");
-    if (b == 0) return DAPOL_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t tot = b * (size_t)H;
-    DevBuf<uint64_t> dl;
-    DevBuf<uint32_t> dC, dH, dout, dtape;
-    HIPCHK(dl.alloc(b)); HIPCHK(dC.alloc(tot * 8)); HIPCHK(dH.alloc(tot * (size_t)ctx_hw(ctx))); HIPCHK(dout.alloc(b * es / 4)); HIPCHK(dtape.alloc(b * slots * 16));
-    HIPCHK(hipMemcpyAsync(dl.p, leaf_idx, b * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dtape.p, tape, b * slots * 64, hipMemcpyHostToDevice, st));
-    int32_t rc = prove_entities_device(ctx, tree, b, dl.p, policy, aggregation_factor, n_bits, nullptr, UpperSibs{}, dC.p, dH.p, dout.p, nullptr, dtape.p, slots);
-    if (rc) return rc;
-    if (path_C32) HIPCHK(hipMemcpy(path_C32, dC.p, tot * 32, hipMemcpyDeviceToHost));
-    if (path_H32) HIPCHK(hipMemcpy(path_H32, dH.p, tot * ctx_hash_bytes(ctx), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(range_out, dout.p, b * es, hipMemcpyDeviceToHost));
-    return DAPOL_OK;
-}
-int32_t dapol_prove_entities(dapol_ctx* ctx, dapol_tree* tree, size_t b, const uint64_t* leaf_idx, int32_t policy,
-                             int32_t aggregation_factor, int32_t n_bits, const uint8_t nonce_seed32[32], uint8_t* path_C32,
-                             uint8_t* path_H32, uint8_t* range_out) {
-    WIRE_SCOPE();
-    return dapol_prove_entities_upper(ctx, tree, b, leaf_idx, policy, aggregation_factor, n_bits, nonce_seed32, 0, nullptr, nullptr, nullptr,
-                                      nullptr, path_C32, path_H32, range_out);
-}
-
-// ------------------------------------------------------------------------------------------------ workload
-struct dapol_workload {
-    dapol_ctx* ctx = nullptr;
-    int total_height = 0, shard_bits = 0;
-    size_t n = 0;
-    DevBuf<uint64_t> idx, v;
-    DevBuf<uint32_t> r;
-    DevBuf<uint32_t> proofs, pathC, pathH;     // outputs of the last prove
-    size_t proofs_first = 0, proofs_count = 0, proof_words = 0;
-    DevBuf<unsigned long long> csum;
-    DevBuf<uint32_t> seed;
-    dapol_tree_owned* tree = nullptr;          // last build (borrows idx / v / r)
-    bool holds_ctx = false;
-    ~dapol_workload() { delete tree; }
-};
-
-__global__ void k_checksum(size_t n_words, const uint32_t* w, unsigned long long* acc) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long s = 0;
-    for (; i < n_words; i += (size_t)gridDim.x * blockDim.x) s += (unsigned long long)w[i] * (unsigned long long)(2 * (i & 0xffff) + 1);
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_down(s, off);
-    if ((threadIdx.x & 63) == 0) atomicAdd(acc, s);
-}
-
-int32_t dapol_workload_create_shard(dapol_ctx* ctx, int32_t total_height, int32_t shard_bits, size_t n, const uint64_t* leaf_idx,
-                                    const uint64_t* v, const uint8_t* r32, dapol_workload** out) {
-    if (!ctx || !out || !n || !leaf_idx || !v || !r32) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    NEEDS_32_BYTE_DIGEST(ctx, "the device-resident workload (bench) path");
-    if (total_height < 1 || total_height > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must be in [1, 64]");
-    if (shard_bits < 0 || shard_bits >= total_height || shard_bits > 16) return fail(DAPOL_ERR_INVALID_ARGUMENT, "shard_bits out of range");
-    HIPCHK(hipSetDevice(ctx->device));
-    dapol_workload* w = new dapol_workload();
-    struct Guard { dapol_workload* w; ~Guard() { delete w; } } guard{w};
-    w->ctx = ctx; w->total_height = total_height; w->shard_bits = shard_bits; w->n = n;
-    HIPCHK(w->idx.alloc(n)); HIPCHK(w->v.alloc(n)); HIPCHK(w->r.alloc(n * 8)); HIPCHK(w->csum.alloc(1)); HIPCHK(w->seed.alloc(8));
-    HIPCHK(hipMemcpy(w->idx.p, leaf_idx, n * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(w->v.p, v, n * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(w->r.p, r32, n * 32, hipMemcpyHostToDevice));
-    guard.w = nullptr;
-    w->holds_ctx = true;
-    ctx_retain(ctx);
-    *out = w;
-    return DAPOL_OK;
-}
-int32_t dapol_workload_create(dapol_ctx* ctx, int32_t height, size_t n, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32,
-                              dapol_workload** out) {
-    return dapol_workload_create_shard(ctx, height, 0, n, leaf_idx, v, r32, out);
-}
-int32_t dapol_workload_destroy(dapol_workload* w) {
-    if (!w) return DAPOL_OK;
-    dapol_ctx* ctx = w->holds_ctx ? w->ctx : nullptr;
-    if (w->ctx) (void)hipSetDevice(w->ctx->device);
-    delete w;
-    if (ctx) (void)dapol_ctx_destroy(ctx);
-    return DAPOL_OK;
-}
-
-int32_t dapol_workload_tree(dapol_workload* w, dapol_tree** out) {
-    if (!w || !out) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    if (!w->tree) return fail(DAPOL_ERR_INVALID_ARGUMENT, "dapol_workload_build has not run");
-    *out = w->tree;
-    return DAPOL_OK;
-}
-
-int32_t dapol_workload_build(dapol_workload* w, const uint8_t pad_seed32[32], uint8_t root_C[32], uint8_t root_H[32], uint64_t* root_v,
-                             uint8_t root_r[32], dapol_workload_stats* stats) {
-    if (!w || !pad_seed32) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    dapol_ctx* ctx = w->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    EventPair ev;
-    HIPCHK(ev.init());
-    {   // The new tree takes over the arena of the previous build (same leaves => same bounds => same size): a step neither frees
-        // nor allocates the 3 GB, and the first timed step of a run no longer pays a cold hipMalloc (340 ms against a 45 ms build).
-        dapol_tree_owned* old = w->tree;
-        w->tree = new dapol_tree_owned();
-        if (old) w->tree->arena = std::move(old->arena);
-        delete old;
-    }
-    HIPCHK(hipEventRecord(ev.a, st));
-    int32_t rc = tree_build_device(ctx, w->total_height, w->shard_bits, w->n, w->idx.p, w->v.p, w->r.p, pad_seed32, w->tree);
-    if (rc) { delete w->tree; w->tree = nullptr; return rc; }
-    HIPCHK(hipEventRecord(ev.b, st));
-    LevelView root = w->tree->view(w->tree->height, nullptr);
-    if (root_C) HIPCHK(hipMemcpyAsync(root_C, root.C, 32, hipMemcpyDeviceToHost, st));
-    if (root_H) HIPCHK(hipMemcpyAsync(root_H, root.H, 32, hipMemcpyDeviceToHost, st));
-    if (root_v) HIPCHK(hipMemcpyAsync(root_v, root.v, 8, hipMemcpyDeviceToHost, st));
-    if (root_r) HIPCHK(hipMemcpyAsync(root_r, root.r, 32, hipMemcpyDeviceToHost, st));
-    if (stats) {
-        HIPCHK(hipMemcpyAsync(stats->root_C, root.C, 32, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(stats->root_H, root.H, 32, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    if (stats) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
-        stats->tree_ms = ms;
-    }
-    return DAPOL_OK;
-}
-
-int32_t dapol_workload_prove(dapol_workload* w, const uint8_t nonce_seed32[32], int32_t n_bits, size_t first_entity, size_t n_entities,
-                             int32_t n_upper, const uint8_t* up_C32, const uint8_t* up_H32, const uint64_t* up_v, const uint8_t* up_r32,
-                             dapol_workload_stats* stats) {
-    return dapol_workload_prove_policy(w, nonce_seed32, n_bits, first_entity, n_entities, DAPOL_POLICY_PADDING, w ? w->total_height : 0, n_upper, up_C32, up_H32,
-                                       up_v, up_r32, stats);
-}
-
-int32_t dapol_workload_prove_policy(dapol_workload* w, const uint8_t nonce_seed32[32], int32_t n_bits, size_t first_entity, size_t n_entities,
-                                    int32_t policy, int32_t aggregation_factor, int32_t n_upper, const uint8_t* up_C32, const uint8_t* up_H32,
-                                    const uint64_t* up_v, const uint8_t* up_r32, dapol_workload_stats* stats) {
-    WIRE_SCOPE();
-    if (!w || !nonce_seed32 || !stats) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    if (!w->tree) return fail(DAPOL_ERR_INVALID_ARGUMENT, "dapol_workload_build has not run");
-    if (n_upper != w->shard_bits) return fail(DAPOL_ERR_INVALID_ARGUMENT, "n_upper must equal the workload's shard_bits");
-    if (first_entity > w->n || n_entities > w->n - first_entity) return fail(DAPOL_ERR_INVALID_ARGUMENT, "entity range out of bounds");
-    dapol_ctx* ctx = w->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int Htot = w->total_height;
-    size_t es = dapol_entity_proof_size(Htot, policy, aggregation_factor, n_bits);
-    if (es == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation factor / n_bits");
-    EventPair ev;
-    HIPCHK(ev.init());
-    const size_t tot = n_entities * (size_t)Htot;
-    if (w->proofs.n < n_entities * es / 4) HIPCHK(w->proofs.alloc(n_entities * es / 4));
-    if (w->pathC.n < tot * 8) { HIPCHK(w->pathC.alloc(tot * 8)); HIPCHK(w->pathH.alloc(tot * 8)); }
-    HIPCHK(hipMemcpyAsync(w->seed.p, nonce_seed32, 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(w->csum.p, 0, 8, st));
-    UpperDev up;
-    int32_t rc = up.upload(st, n_upper, up_C32, up_H32, up_v, up_r32);
-    if (rc) return rc;
-    MsmTiming tm;
-    tm.enabled = true;
-    HIPCHK(hipEventRecord(ev.a, st));
-    if (n_entities) {
-        rc = prove_entities_device(ctx, w->tree, n_entities, w->idx.p + first_entity, policy, aggregation_factor, n_bits, w->seed.p, up.view,
-                                   w->pathC.p, w->pathH.p, w->proofs.p, &tm);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(ev.b, st));
-    if (n_entities) {
-        hipLaunchKernelGGL(k_checksum, dim3(1024), dim3(256), 0, st, n_entities * es / 4, w->proofs.p, w->csum.p); LAUNCH_CHECK();
-    }
-    unsigned long long cs = 0;
-    HIPCHK(hipMemcpyAsync(&cs, w->csum.p, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    stats->prove_ms = ms;
-    stats->msm_ms = tm.total_ms(0); stats->msm_launches = tm.launches(0);
-    stats->mat_ms = tm.total_ms(1); stats->mat_launches = tm.launches(1);
-    stats->msm_all_ms = tm.total_ms(-1);
-    stats->msm_span_ms = tm.span_ms(0);
-    stats->msm_kernels = tm.kernels[0]; stats->mat_kernels = tm.kernels[1];
-    stats->proofs = n_entities; stats->proof_bytes = n_entities * es; stats->checksum = cs;
-    w->proofs_first = first_entity; w->proofs_count = n_entities; w->proof_words = es / 4;
-    return DAPOL_OK;
-}
-
-int32_t dapol_workload_run(dapol_workload* w, const uint8_t pad_seed32[32], const uint8_t nonce_seed32[32], int32_t n_bits,
-                           size_t first_entity, size_t n_entities, dapol_workload_stats* stats) {
-    if (!w || !stats) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    if (w->shard_bits != 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "sharded workloads use dapol_workload_build + dapol_workload_prove");
-    memset(stats, 0, sizeof *stats);
-    int32_t rc = dapol_workload_build(w, pad_seed32, nullptr, nullptr, nullptr, nullptr, stats);
-    if (rc) return rc;
-    return dapol_workload_prove(w, nonce_seed32, n_bits, first_entity, n_entities, 0, nullptr, nullptr, nullptr, nullptr, stats);
-}
-
-int32_t dapol_workload_paths(dapol_workload* w, size_t b, const uint64_t* leaf_idx, int32_t n_upper, const uint64_t* up_v,
-                             const uint8_t* up_r32, const uint8_t* up_C32, const uint8_t* up_H32, uint64_t* sib_v, uint8_t* sib_r32,
-                             uint8_t* sib_C32, uint8_t* sib_H32) {
-    WIRE_SCOPE();
-    if (!w || !w->tree || (b && !leaf_idx)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument / no build yet");
-    if (n_upper != w->shard_bits) return fail(DAPOL_ERR_INVALID_ARGUMENT, "n_upper must equal the workload's shard_bits");
-    if (b == 0) return DAPOL_OK;
-    dapol_ctx* ctx = w->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int Htot = w->total_height;
-    const size_t tot = b * (size_t)Htot;
-    DevBuf<uint64_t> dl, dv, duv;
-    DevBuf<uint32_t> dr, dC, dH, dpos, dur, duC, duH;
-    HIPCHK(dl.alloc(b)); HIPCHK(dpos.alloc(b)); HIPCHK(dv.alloc(tot)); HIPCHK(dr.alloc(tot * 8)); HIPCHK(dC.alloc(tot * 8)); HIPCHK(dH.alloc(tot * 8));
-    HIPCHK(hipMemcpyAsync(dl.p, leaf_idx, b * 8, hipMemcpyHostToDevice, st));
-    PathOut po{dC.p, dH.p, dv.p, dr.p};
-    int32_t rc = tree_paths_device(w->tree, b, dl.p, po, dpos.p, n_upper);
-    if (rc) return rc;
-    if (n_upper) {
-        const size_t u = (size_t)n_upper;
-        std::vector<uint8_t> zeros(u * 32, 0);
-        std::vector<uint64_t> zv(u, 0);
-        HIPCHK(duv.alloc(u)); HIPCHK(dur.alloc(u * 8)); HIPCHK(duC.alloc(u * 8)); HIPCHK(duH.alloc(u * 8));
-        HIPCHK(hipMemcpyAsync(duv.p, up_v ? up_v : zv.data(), u * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(dur.p, up_r32 ? up_r32 : zeros.data(), u * 32, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(duC.p, up_C32 ? up_C32 : zeros.data(), u * 32, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(duH.p, up_H32 ? up_H32 : zeros.data(), u * 32, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_tree_path_upper, dim3(nblk(b * u, 256)), dim3(256), 0, st, b, w->tree->height, n_upper, g_wire.siblings_leaf_first, duC.p, duH.p, duv.p, dur.p, po);
-        LAUNCH_CHECK();
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    if (sib_v) HIPCHK(hipMemcpyAsync(sib_v, dv.p, tot * 8, hipMemcpyDeviceToHost, st));
-    if (sib_r32) HIPCHK(hipMemcpyAsync(sib_r32, dr.p, tot * 32, hipMemcpyDeviceToHost, st));
-    if (sib_C32) HIPCHK(hipMemcpyAsync(sib_C32, dC.p, tot * 32, hipMemcpyDeviceToHost, st));
-    if (sib_H32) HIPCHK(hipMemcpyAsync(sib_H32, dH.p, tot * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return DAPOL_OK;
-}
-
-int32_t dapol_workload_proofs(dapol_workload* w, size_t first, size_t count, uint8_t* out) {
-    if (!w || (count && !out)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    if (first < w->proofs_first || first - w->proofs_first > w->proofs_count || count > w->proofs_count - (first - w->proofs_first))
-        return fail(DAPOL_ERR_INVALID_ARGUMENT, "proof range not part of the last run");
-    HIPCHK(hipSetDevice(w->ctx->device));
-    HIPCHK(hipMemcpy(out, w->proofs.p + (first - w->proofs_first) * w->proof_words, count * w->proof_words * 4, hipMemcpyDeviceToHost));
-    return DAPOL_OK;
-}
-
-// verification lives in host_verify.inc
-#include "host_verify.inc"

@@ -91,52 +91,33 @@ int32_t dapol_reprove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b
                                       const uint8_t* old_range, uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out, uint64_t* proved_out,
                                       uint64_t* kept_out) {
     WIRE_SCOPE();
-    if (!ctx || !tree || tree->ctx != ctx || !nonce_seed32 || (b && (!leaf_idx || !range_out)))
-        return fail(DAPOL_ERR_INVALID_ARGUMENT, "null or out-of-range argument");
-    const int H = tree->height;
-    if (H > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
-    const size_t es = dapol_entity_proof_size(H, policy, aggregation_factor, n_bits);
-    if (es == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation_factor / n_bits");
-    std::vector<SubProof> plan;
-    policy_plan(policy, H, aggregation_factor, plan);
-    for (auto& s : plan)
-        if (s.m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
+    EntityShape S;
+    int32_t rc = entity_shape(ctx, tree, nonce_seed32 && (!b || (leaf_idx && range_out)), "null or out-of-range argument", 0, policy, aggregation_factor, n_bits,
+                              true, true, S);
+    if (rc) return rc;
     if (!strictly_increasing(b, leaf_idx)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "leaf indexes must be strictly increasing");
     bool any_old = has_old == nullptr && b > 0;
     for (size_t e = 0; has_old && e < b && !any_old; e++) any_old = has_old[e] != 0;
     if (any_old && (!old_path_C32 || !old_range))
         return fail(DAPOL_ERR_INVALID_ARGUMENT, "old_path_C32 and old_range are needed while some row has old data (has_old set, or NULL)");
-    if (b == 0) {
-        if (proved_out) *proved_out = 0;
-        if (kept_out) *kept_out = 0;
-        return DAPOL_OK;
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t tot = b * (size_t)H;
-    DevBuf<uint64_t> dl, pv;
-    DevBuf<uint32_t> dseed, dC, dH, dout, pr, pos, doldC;
-    DevBuf<uint8_t> dhas;
-    HIPCHK(dl.alloc(b)); HIPCHK(dseed.alloc(8)); HIPCHK(dC.alloc(tot * 8)); HIPCHK(dH.alloc(tot * (size_t)ctx_hw(ctx))); HIPCHK(dout.alloc(b * es / 4));
-    HIPCHK(pv.alloc(tot)); HIPCHK(pr.alloc(tot * 8)); HIPCHK(pos.alloc(b));
-    // every input goes up before anything is written back: the outputs may alias the old arrays
-    HIPCHK(hipMemcpyAsync(dl.p, leaf_idx, b * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dseed.p, nonce_seed32, 32, hipMemcpyHostToDevice, st));
-    if (has_old) { HIPCHK(dhas.alloc(b)); HIPCHK(hipMemcpyAsync(dhas.p, has_old, b, hipMemcpyHostToDevice, st)); }
-    if (any_old) {
-        HIPCHK(doldC.alloc(tot * 8));
-        if (tot) HIPCHK(hipMemcpyAsync(doldC.p, old_path_C32, tot * 32, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(dout.p, old_range, b * es, hipMemcpyHostToDevice, st));      // the old blobs ARE the output buffer: kept rows never move
-    }
-    PathOut po{dC.p, dH.p, pv.p, pr.p};
-    int32_t rc = tree_paths_device(tree, b, dl.p, po, pos.p, 0);
-    if (rc) return rc;
     uint64_t proved = 0, kept = 0;
-    rc = reprove_policy_device(ctx, plan, b, H, pv.p, pr.p, dC.p, n_bits, dseed.p, dl.p, dhas.p, doldC.p, dout.p, &proved, &kept);
-    if (rc) return rc;
-    if (path_C32) HIPCHK(hipMemcpy(path_C32, dC.p, tot * 32, hipMemcpyDeviceToHost));
-    if (path_H32) HIPCHK(hipMemcpy(path_H32, dH.p, tot * ctx_hash_bytes(ctx), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(range_out, dout.p, b * es, hipMemcpyDeviceToHost));
+    if (b) {
+        EntityProveCall call;
+        DevBuf<uint32_t> doldC;
+        DevBuf<uint8_t> dhas;
+        hipStream_t st = ctx->stream;
+        // every input goes up before anything is written back: the outputs may alias the old arrays
+        if ((rc = call.open(ctx, tree, S, b, leaf_idx, nonce_seed32, 0, nullptr, nullptr, nullptr, nullptr))) return rc;
+        if (has_old) { HIPCHK(dhas.alloc(b)); HIPCHK(hipMemcpyAsync(dhas.p, has_old, b, hipMemcpyHostToDevice, st)); }
+        if (any_old) {
+            HIPCHK(doldC.alloc(call.tot * 8));
+            if (call.tot) HIPCHK(hipMemcpyAsync(doldC.p, old_path_C32, call.tot * 32, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(call.out.p, old_range, b * S.es, hipMemcpyHostToDevice, st));      // the old blobs ARE the output buffer: kept rows never move
+        }
+        if ((rc = call.paths())) return rc;
+        rc = reprove_policy_device(ctx, S.plan, b, S.H, call.pv.p, call.pr.p, call.pathC.p, n_bits, call.seed.p, call.idx.p, dhas.p, doldC.p, call.out.p, &proved, &kept);
+        if (rc || (rc = call.download(path_C32, path_H32, range_out))) return rc;
+    }
     if (proved_out) *proved_out = proved;
     if (kept_out) *kept_out = kept;
     return DAPOL_OK;

@@ -142,48 +142,18 @@ int32_t dapol_prove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b, 
                                     const uint64_t* up_v, const uint8_t* up_r32, uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out,
                                     uint64_t* unique_subproofs_out) {
     WIRE_SCOPE();
-    if (!ctx || !tree || tree->ctx != ctx || !nonce_seed32 || (b && (!leaf_idx || !range_out)) || n_upper < 0 || n_upper > 16)
-        return fail(DAPOL_ERR_INVALID_ARGUMENT, "null or out-of-range argument");
-    if (n_upper) NEEDS_32_BYTE_DIGEST(ctx, "the sharded (multi-GPU) path");
-    const int H = tree->height + n_upper;
-    if (H > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
-    const size_t es = dapol_entity_proof_size(H, policy, aggregation_factor, n_bits);
-    if (es == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation_factor / n_bits");
-    std::vector<SubProof> plan;
-    policy_plan(policy, H, aggregation_factor, plan);
-    for (auto& s : plan)
-        if (s.m > ctx->max_parties) return fail(DAPOL_ERR_INVALID_ARGUMENT, "aggregation needs more parties than the context was created for");
+    EntityShape S;
+    int32_t rc = entity_shape(ctx, tree, nonce_seed32 && (!b || (leaf_idx && range_out)), "null or out-of-range argument", n_upper, policy, aggregation_factor,
+                              n_bits, true, true, S);
+    if (rc) return rc;
     if (!strictly_increasing(b, leaf_idx)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "leaf indexes must be strictly increasing");
-    if (b == 0) {
-        if (unique_subproofs_out) *unique_subproofs_out = 0;
-        return DAPOL_OK;
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t tot = b * (size_t)H;
-    DevBuf<uint64_t> dl, pv;
-    DevBuf<uint32_t> dseed, dC, dH, dout, pr, pos;
-    UpperDev up;
-    HIPCHK(dl.alloc(b)); HIPCHK(dseed.alloc(8)); HIPCHK(dC.alloc(tot * 8)); HIPCHK(dH.alloc(tot * (size_t)ctx_hw(ctx))); HIPCHK(dout.alloc(b * es / 4));
-    HIPCHK(pv.alloc(tot)); HIPCHK(pr.alloc(tot * 8)); HIPCHK(pos.alloc(b));
-    HIPCHK(hipMemcpyAsync(dl.p, leaf_idx, b * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dseed.p, nonce_seed32, 32, hipMemcpyHostToDevice, st));
-    int32_t rc = up.upload(st, n_upper, up_C32, up_H32, up_v, up_r32);
-    if (rc) return rc;
-    PathOut po{dC.p, dH.p, pv.p, pr.p};
-    rc = tree_paths_device(tree, b, dl.p, po, pos.p, n_upper);
-    if (rc) return rc;
-    if (n_upper) {
-        hipLaunchKernelGGL(k_tree_path_upper, dim3(nblk(b * (size_t)n_upper, 256)), dim3(256), 0, st, b, tree->height, n_upper, g_wire.siblings_leaf_first,
-                           up.view.C, up.view.H, up.view.v, up.view.r, po);
-        LAUNCH_CHECK();
-    }
     uint64_t unique = 0;
-    rc = prove_policy_shared_device(ctx, plan, b, H, pv.p, pr.p, dC.p, n_bits, dseed.p, dl.p, dout.p, &unique);
-    if (rc) return rc;
-    if (path_C32) HIPCHK(hipMemcpy(path_C32, dC.p, tot * 32, hipMemcpyDeviceToHost));
-    if (path_H32) HIPCHK(hipMemcpy(path_H32, dH.p, tot * ctx_hash_bytes(ctx), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(range_out, dout.p, b * es, hipMemcpyDeviceToHost));
+    if (b) {
+        EntityProveCall call;
+        if ((rc = call.open(ctx, tree, S, b, leaf_idx, nonce_seed32, n_upper, up_C32, up_H32, up_v, up_r32)) || (rc = call.paths())) return rc;
+        rc = prove_policy_shared_device(ctx, S.plan, b, S.H, call.pv.p, call.pr.p, call.pathC.p, n_bits, call.seed.p, call.idx.p, call.out.p, &unique);
+        if (rc || (rc = call.download(path_C32, path_H32, range_out))) return rc;
+    }
     if (unique_subproofs_out) *unique_subproofs_out = unique;
     return DAPOL_OK;
 }

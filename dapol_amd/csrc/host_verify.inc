@@ -1,4 +1,4 @@
-// Batched verifier host side (kernels in kernels_verify.h).
+// Batched verifier host side (kernels in kernels_verify.h).  Included from dapol_hip.hip after the prover's files.
 // Device-pointer core: proofs at d_proofs + e*stride_words (+ the caller's offset already applied), commitments [b][m][8],
 // verdicts to d_ok[b].
 // The m commitments of a many-party proof are absorbed by one wavefront per proof (k_rv_absorb_V); inclusion proofs
@@ -406,7 +406,7 @@ int32_t dapol_range_verify_batch(dapol_ctx* ctx, int32_t n_bits, int32_t m, size
 // R::verify (src/range/padding.rs:169-196, splitting.rs:181-210) for b proofs over H sibling commitments each
 // (dPC: [b][H][8]); ANDs the verdicts into dok.  dsub: [b] bytes, dV: [b][max m][8] scratch.
 // A run of equal-sized FULL sub-proofs (the individual proofs beyond aggregation_factor, with the one-party part of an odd split before
-// them -- as the prover groups them, host_range.inc) is ONE batched check of b * k proofs: their words gathered into a contiguous
+// them -- as the prover groups them, host_policy.inc) is ONE batched check of b * k proofs: their words gathered into a contiguous
 // batch, commitments [b * k][m], the entity's verdict the AND over its k sub-proofs (round 6; DAPOL_NO_GROUP=1: one check per sub-proof).
 static int32_t verify_policy_device(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t b, int H, const uint32_t* dPC, const uint32_t* dR,
                                     size_t entity_words, int n_bits, const uint32_t* dseed, uint8_t* dok, uint8_t* dsub, uint32_t* dV) {
@@ -414,7 +414,18 @@ static int32_t verify_policy_device(dapol_ctx* ctx, const std::vector<SubProof>&
     const uint32_t* Bb_comp = ctx->gens_comp.p + (size_t)ctx->tv.row_Bb(0) * 8;
     const PolicyGroups PG = group_policy_plan(plan, policy_grouping_on());
     const std::vector<PolicyGroup>& groups = PG.groups;
-    auto words_of = [&](const PolicyGroup& g) { return dapol_range_proof_size(n_bits, g.m) / 4; };
+    const bool on_lanes = verify_groups_on_lanes(groups.size(), b, PG.sum_proofs, PG.max_k, ctx->opt.verify_batch_min);
+    const PolicyLayout L = policy_layout(PG, b, n_bits, !on_lanes);
+    // What the checks need beside the caller's [b]-sized buffers: the gathered words, commitments and verdicts of every group (on lanes)
+    // or of the largest one (one after the other: only runs of several sub-proofs are gathered, a lone one is read in place).
+    DevBuf<uint32_t> arena;
+    uint32_t *aR = nullptr, *aV = nullptr;
+    uint8_t* asub = nullptr;
+    if (on_lanes || PG.max_k > 1) {
+        const size_t o_V = align_up(L.words * 4, 256), o_sub = o_V + align_up(L.parties * 32, 256), total = o_sub + align_up(L.proofs, 256);
+        HIPCHK(arena.alloc(total / 4 + 64));
+        aR = arena.p; aV = (uint32_t*)((uint8_t*)arena.p + o_V); asub = (uint8_t*)arena.p + o_sub;
+    }
     // one group's commitments, [b * k][m]: an aggregated (or lone individual) proof pads its parties, a run of full ones does not
     auto gather_commitments = [&](const PolicyGroup& g, uint32_t* out) -> int32_t {
         if (g.k == 1) hipLaunchKernelGGL(k_gather_commitments, dim3(nblk(b * (size_t)g.m, 256)), dim3(256), 0, st, b, H, g.start, g.count, g.m, dPC, Bb_comp, out);
@@ -422,85 +433,55 @@ static int32_t verify_policy_device(dapol_ctx* ctx, const std::vector<SubProof>&
         LAUNCH_CHECK();
         return DAPOL_OK;
     };
-    auto gather_words = [&](const PolicyGroup& g, size_t word_off, uint32_t* out) -> int32_t {
-        hipLaunchKernelGGL(k_gather_words_grouped, dim3(nblk(b * (size_t)g.k * words_of(g), 256)), dim3(256), 0, st, b, g.k, words_of(g), entity_words, word_off, dR, out);
+    auto gather_words = [&](size_t gi) -> int32_t {
+        const PolicyLayout::Group& lg = L.g[gi];
+        hipLaunchKernelGGL(k_gather_words_grouped, dim3(nblk(b * (size_t)groups[gi].k * lg.proof_words, 256)), dim3(256), 0, st, b, groups[gi].k, lg.proof_words,
+                           entity_words, lg.word_off, dR, aR + lg.gathered_word_off);
         LAUNCH_CHECK();
         return DAPOL_OK;
     };
-    // A SMALL call with several groups (as the prover, host_range.inc): the per-proof checks of the groups side by side, each on a
-    // lane of its own, queued without a host wait; the verdicts are ANDed on the context's stream behind the lanes' events.
-    if (verify_groups_on_lanes(groups.size(), b, PG.sum_proofs, PG.max_k, ctx->opt.verify_batch_min)) {
-        size_t sum_words = 0;
-        for (auto& g : groups) sum_words += (size_t)g.k * words_of(g);
-        DevBuf<uint32_t> arena;
-        const size_t o_V = align_up(b * sum_words * 4, 256), o_sub = o_V + align_up(b * PG.sum_parties * 32, 256), total = o_sub + align_up(b * PG.sum_proofs, 256);
-        HIPCHK(arena.alloc(total / 4 + 64));
-        uint32_t* const aR = arena.p;
-        uint32_t* const aV = (uint32_t*)((uint8_t*)arena.p + o_V);
-        uint8_t* const asub = (uint8_t*)arena.p + o_sub;
-        std::vector<size_t> offR(groups.size()), offV(groups.size()), offS(groups.size());
-        size_t word_off = 0, r_off = 0, v_off = 0, s_off = 0;
-        int32_t rc = DAPOL_OK;
+    int32_t rc = DAPOL_OK;
+    if (!on_lanes) {
         for (size_t gi = 0; gi < groups.size(); gi++) {
-            auto& g = groups[gi];
-            const size_t pw = words_of(g), np = b * (size_t)g.k;
-            offR[gi] = r_off; offV[gi] = v_off; offS[gi] = s_off;
-            if ((rc = gather_commitments(g, aV + v_off * 8)) || (rc = gather_words(g, word_off, aR + r_off))) return rc;
-            word_off += pw * (size_t)g.k; r_off += np * pw; v_off += np * (size_t)g.m; s_off += np;
-        }
-        HIPCHK(hipEventRecord(ctx->ev_v[0], st));
-        std::vector<dapol_ctx*> lanes(groups.size(), nullptr);
-        for (size_t gi = 0; gi < groups.size() && !rc; gi++) {
-            auto& g = groups[gi];
-            rc = ctx_lane(ctx, (int)(gi % 4), &lanes[gi]);
-            if (rc) break;
-            dapol_ctx* lane = lanes[gi];
-            if (lane != ctx) HIPCHK(hipStreamWaitEvent(lane->stream, ctx->ev_v[0], 0));
-            rc = range_verify_device(lane, verify_shape(lane, n_bits, g.m, b * (size_t)g.k), aR + offR[gi], words_of(g), aV + offV[gi] * 8, dseed, asub + offS[gi], true);
-            if (rc) break;
-            if (lane != ctx) {                                  // the context's stream takes the verdicts behind the lane (one event per lane and use)
-                HIPCHK(hipEventRecord(lane->ev_v[1 + (gi / 4) % 3], lane->stream));
-                HIPCHK(hipStreamWaitEvent(st, lane->ev_v[1 + (gi / 4) % 3], 0));
+            const PolicyGroup& g = groups[gi];
+            const PolicyLayout::Group& lg = L.g[gi];
+            if ((rc = gather_commitments(g, g.k == 1 ? dV : aV))) return rc;
+            if (g.k == 1) {                                     // (its words are read in place, an entity's blob apart)
+                if ((rc = range_verify_rlc_device(ctx, n_bits, g.m, b, dR + lg.word_off, entity_words, dV, dseed, dsub))) return rc;
+                hipLaunchKernelGGL(k_and_bytes, dim3(nblk(b, 256)), dim3(256), 0, st, b, dok, dsub);
+            } else {
+                if ((rc = gather_words(gi)) || (rc = range_verify_rlc_device(ctx, n_bits, g.m, b * (size_t)g.k, aR, lg.proof_words, aV, dseed, asub))) return rc;
+                hipLaunchKernelGGL(k_and_bytes_grouped, dim3(nblk(b, 256)), dim3(256), 0, st, b, g.k, dok, asub);
             }
-            hipLaunchKernelGGL(k_and_bytes_grouped, dim3(nblk(b, 256)), dim3(256), 0, st, b, g.k, dok, asub + offS[gi]);
             LAUNCH_CHECK();
         }
-        for (auto* l : lanes) if (l && l != ctx) (void)hipStreamSynchronize(l->stream);      // (every lane drains before the arena is freed)
-        HIPCHK(hipStreamSynchronize(st));
-        return rc;
+        HIPCHK(hipStreamSynchronize(st));                      // (the arena dies with this scope)
+        return DAPOL_OK;
     }
-    size_t g_words = 0, g_parties = 0, g_proofs = 0;           // what the grouped checks need beside the caller's [b]-sized buffers
-    for (auto& g : groups)
-        if (g.k > 1) {
-            g_words = std::max(g_words, b * (size_t)g.k * words_of(g));
-            g_parties = std::max(g_parties, b * (size_t)g.k * (size_t)g.m);
-            g_proofs = std::max(g_proofs, b * (size_t)g.k);
-        }
-    DevBuf<uint32_t> garena;
-    uint32_t *gR = nullptr, *gV = nullptr;
-    uint8_t* gsub = nullptr;
-    if (g_proofs) {
-        const size_t o_V = align_up(g_words * 4, 256), o_sub = o_V + align_up(g_parties * 32, 256), total = o_sub + align_up(g_proofs, 256);
-        HIPCHK(garena.alloc(total / 4 + 64));
-        gR = garena.p; gV = (uint32_t*)((uint8_t*)garena.p + o_V); gsub = (uint8_t*)garena.p + o_sub;
-    }
-    size_t word_off = 0;
-    for (auto& g : groups) {
-        const size_t pw = words_of(g);
-        int32_t rc = gather_commitments(g, g.k == 1 ? dV : gV);
+    // A SMALL call with several groups (as the prover, host_policy.inc): the per-proof checks of the groups side by side, each on a
+    // lane of its own, queued without a host wait; the verdicts are ANDed on the context's stream behind the lanes' events.
+    PolicyLanes lanes(ctx);                                    // (an early return below: it waits for the lanes before the arena goes)
+    for (size_t gi = 0; gi < groups.size(); gi++)
+        if ((rc = gather_commitments(groups[gi], aV + L.g[gi].party_off * 8)) || (rc = gather_words(gi))) return rc;
+    if ((rc = lanes.fork(st))) return rc;
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        if (gi == 2) FAULT_AFTER_FORK("policy_verify_lanes");     // (group 1 is in flight on a lane of its own)
+        const PolicyGroup& g = groups[gi];
+        const PolicyLayout::Group& lg = L.g[gi];
+        dapol_ctx* lane = nullptr;
+        if ((rc = lanes.take(gi, &lane))) return rc;
+        rc = range_verify_device(lane, verify_shape(lane, n_bits, g.m, b * (size_t)g.k), aR + lg.gathered_word_off, lg.proof_words, aV + lg.party_off * 8, dseed,
+                                 asub + lg.verdict_off, true);
         if (rc) return rc;
-        if (g.k == 1) {                                         // (its words are read in place, an entity's blob apart)
-            rc = range_verify_rlc_device(ctx, n_bits, g.m, b, dR + word_off, entity_words, dV, dseed, dsub);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_and_bytes, dim3(nblk(b, 256)), dim3(256), 0, st, b, dok, dsub);
-        } else {
-            if ((rc = gather_words(g, word_off, gR)) || (rc = range_verify_rlc_device(ctx, n_bits, g.m, b * (size_t)g.k, gR, pw, gV, dseed, gsub))) return rc;
-            hipLaunchKernelGGL(k_and_bytes_grouped, dim3(nblk(b, 256)), dim3(256), 0, st, b, g.k, dok, gsub);
+        if (lane != ctx) {                                      // the context's stream takes the verdicts behind the lane (one event per lane and use)
+            HIPCHK(hipEventRecord(lane->ev_v[1 + (gi / 4) % 3], lane->stream));
+            HIPCHK(hipStreamWaitEvent(st, lane->ev_v[1 + (gi / 4) % 3], 0));
         }
+        hipLaunchKernelGGL(k_and_bytes_grouped, dim3(nblk(b, 256)), dim3(256), 0, st, b, g.k, dok, asub + lg.verdict_off);
         LAUNCH_CHECK();
-        word_off += pw * (size_t)g.k;
     }
-    HIPCHK(hipStreamSynchronize(st));                          // (the grouped batch's arena dies with this scope)
+    HIPCHK(hipStreamSynchronize(st));                          // (behind every lane's event: the lanes have drained too)
+    lanes.close();
     return DAPOL_OK;
 }
 

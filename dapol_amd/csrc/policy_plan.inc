@@ -1,7 +1,8 @@
 // Sizes and plans that are pure host arithmetic: which siblings go into which aggregated proof under the two policies, and the
-// byte sizes that follow.  Shared by the library (host_range.inc, host_wire.inc, host_verify.inc) and by the host-only build of
-// the wire parser that runs under AddressSanitizer on the CPU (tests/cpp/wire_asan.cpp).
+// byte sizes that follow.  Shared by the library (host_policy.inc, host_entity.inc, host_wire.inc, host_verify.inc) and by the host-only
+// builds that run under AddressSanitizer on the CPU (tests/cpp/wire_asan.cpp, tests/cpp/policy_group_host.cpp).
 #pragma once
+#include <algorithm>
 #include <vector>
 
 size_t dapol_range_proof_size(int32_t n_bits, int32_t m) {
@@ -56,6 +57,36 @@ static PolicyGroups group_policy_plan(const std::vector<SubProof>& plan, bool gr
         if (parties > G.max_parties) G.max_parties = parties;
     }
     return G;
+}
+
+// Where the groups of a call of b entities live (prove_policy_device, host_policy.inc; verify_policy_device, host_verify.inc).  Per group:
+// its first word inside an entity's blob and first RNG slot inside an entity's draws (one RNG stream runs across an entity's sub-proofs),
+// and its place in the call's GATHERED arrays -- parties / commitments [b * k][m], the verifier's proof words and verdicts [b * k].
+// reuse = false (every group in flight at once, on lanes): the places are running sums and the sizes the totals.
+// reuse = true (one group after the other through the same buffers): the places are 0 and the sizes those of the largest group.
+struct PolicyLayout {
+    struct Group {
+        size_t proof_words;                                 // words of one sub-proof of the group
+        size_t word_off;                                    // inside an entity's blob
+        uint64_t slot_base;                                 // inside an entity's draws
+        size_t party_off, gathered_word_off, verdict_off;   // inside the gathered arrays
+    };
+    std::vector<Group> g;
+    size_t entity_words = 0;                                // one entity's blob: dapol_entity_proof_size / 4
+    size_t parties = 0, words = 0, proofs = 0;              // sizes of the gathered arrays
+};
+static PolicyLayout policy_layout(const PolicyGroups& PG, size_t b, int n_bits, bool reuse) {
+    PolicyLayout L;
+    uint64_t slot = 0;
+    for (auto& pg : PG.groups) {
+        const size_t pw = dapol_range_proof_size(n_bits, pg.m) / 4, np = b * (size_t)pg.k;
+        L.g.push_back({pw, L.entity_words, slot, reuse ? 0 : L.parties, reuse ? 0 : L.words, reuse ? 0 : L.proofs});
+        L.entity_words += pw * (size_t)pg.k;
+        slot += (uint64_t)pg.k * (uint64_t)pg.m * (2 * (uint64_t)n_bits + 4);
+        if (reuse) { L.parties = std::max(L.parties, np * (size_t)pg.m); L.words = std::max(L.words, np * pw); L.proofs = std::max(L.proofs, np); }
+        else { L.parties += np * (size_t)pg.m; L.words += np * pw; L.proofs += np; }
+    }
+    return L;
 }
 
 size_t dapol_entity_proof_size(int32_t height, int32_t policy, int32_t aggregation_factor, int32_t n_bits) {

@@ -3,6 +3,8 @@
    leave that work running on the context's scratch: the ForkGuard waits for it (dapol_diag_fork_guard_waits counts), and the
    next call on the same context gives the oracle's bytes / the right verdicts.  Failures are injected right after each fork
    through the opt-in test knob DAPOL_TEST_FAIL_AFTER_FORK (round-2 advisor finding, round-3 verdict item 8).
+ * The groups of a small call's policy plan run on lanes of their own (dapol_ctx::aux); PolicyLanes (host_policy.inc) waits for every
+   lane it handed out when the prover or the verifier leaves between two groups, and counts in the same counter.
  * dapol_tree_update re-merges in place; a failure between its first and last write leaves a tree that refuses every later
    call instead of proving from upper levels that no longer match the leaves (round-3 advisor finding)."""
 import ctypes
@@ -91,11 +93,17 @@ def test_an_error_after_a_fork_leaves_the_context_clean(hip_lib, ref):
     want32 = ctypes.create_string_buffer(sproofs.size)
     assert ref.ref_range_prove_batch(32, 8, ctypes.c_size_t(4), p(sv), p(sr), SEED, p(np.array([1, 2, 3, 4], np.uint64)), ctypes.c_uint64(0), None, 0, want32) == 0
     assert sproofs.tobytes() == want32.raw
+    # splitting at aggregation 6 over 8 siblings: a 4-party and a 2-party proof and a run of two individual ones -- three groups on three lanes
+    few6C, few6H, few6 = tr.prove_entities(idx[few], 1, 6, n_bits, SEED)
+    verify6 = lambda: ctx.verify_entities(height, idx[few], lC[few], lH[few], few6C, few6H, rC, rH, 1, 6, n_bits, few6, verify_seed=SEED)
+    assert verify6().all()
     sites = [
         ("tree", lambda: hip_lib.Tree(ctx, height, idx, v, r, SEED)),                                          # phased build: leaf commitments on side[0]
         ("prove_A", lambda: ctx.range_prove_batch(32, 8, sv, sr, nonce_seed=SEED, stream_id=[1, 2, 3, 4])),     # small call: A commitment on side[2]
         ("verify_paths", lambda: ctx.verify_entities(height, idx[few], lC[few], lH[few], pC[few], pH[few], rC, rH, 0, height, n_bits, proofs[few], verify_seed=SEED)),
         ("verify_var", lambda: ctx.range_verify_batch(32, 8, sproofs, sC.reshape(4, 8, 32), verify_seed=SEED)),    # small call: own points on side[1]
+        ("policy_prove_lanes", lambda: tr.prove_entities(idx[few], 1, 6, n_bits, SEED)),                           # the second group in flight on lane 1
+        ("policy_verify_lanes", verify6),                                        # the same (16 sub-proofs: the verifier's groups take lanes too)
     ]
     for site, call in sites:
         before = _waits(hip_lib)
@@ -107,8 +115,12 @@ def test_an_error_after_a_fork_leaves_the_context_clean(hip_lib, ref):
                 err = ex
         assert err is not None, "the call never reached the fork at " + site
         assert err.code == 17 and "injected failure after the fork at " + site in str(err), site
-        assert _waits(hip_lib) == before + 1, site                             # the guard waited for exactly the forked stream
+        if site.startswith("policy_"):
+            assert _waits(hip_lib) >= before + 1, site                         # the lane guard (and, in the verifier, the path kernel's fork guard)
+        else:
+            assert _waits(hip_lib) == before + 1, site                         # the guard waited for exactly the forked stream
         clean()
+    assert tr.prove_entities(idx[few], 1, 6, n_bits, SEED)[2].tobytes() == few6.tobytes() and verify6().all()
     # the chunks in flight on the side streams of a multi-chunk prove call (3+ chunks of 64 proofs on two streams)
     ctx.set_options(opts)
     ok_bytes = ctx.range_prove_batch(8, 2, big_v, big_r, nonce_seed=SEED, stream_id=sid)
@@ -156,3 +168,22 @@ def test_failed_in_place_update_marks_the_tree_invalid(hip_lib):
         assert e.value.code == 8 and "left inconsistent" in str(e.value)
     tr.close()                                                                # destroying it is fine, and the context is unharmed
     assert hip_lib.Tree(ctx, 8, idx, v, r, SEED).root() == root0
+
+
+def test_a_fifth_group_shares_the_first_lane(hip_lib):
+    """Splitting at aggregation 31 over 32 siblings: proofs of 16, 8, 4, 2 parties and a run of two individual ones -- five groups, so the
+    fifth goes back to lane 0 (the context itself) and takes the second pinned word.  Same bytes as one group after the other, and valid."""
+    ctx = hip_lib.Context(0, 16)
+    height, n_bits = 32, 8
+    idx, v, r, tr = _small_tree(hip_lib, ctx, height=height, n=4, seed=5)
+    two = idx[:2]
+    pC, pH, proofs = tr.prove_entities(two, 1, 31, n_bits, SEED)
+    with _knob(DAPOL_NO_LANES="1"):
+        qC, qH, serial = tr.prove_entities(two, 1, 31, n_bits, SEED)
+    assert proofs.tobytes() == serial.tobytes() and pC.tobytes() == qC.tobytes() and pH.tobytes() == qH.tobytes()
+    rC, rH, _, _ = tr.root()
+    lC, lH = ctx.commit_hash_batch(v, r)
+    assert ctx.verify_entities(height, two, lC[:2], lH[:2], pC, pH, rC, rH, 1, 31, n_bits, proofs, verify_seed=SEED).all()
+    bad = proofs.copy()
+    bad[1, -40] ^= 1                                                          # (a byte of the last group's proofs, entity 1)
+    assert list(ctx.verify_entities(height, two, lC[:2], lH[:2], pC, pH, rC, rH, 1, 31, n_bits, bad, verify_seed=SEED)) == [1, 0]

@@ -1,6 +1,6 @@
 """Proofs of FEW parties in batches (round 6): the individual proofs a policy leaves per sibling beyond aggregation_factor
 (/root/reference/src/range/padding.rs:104-112, splitting.rs:118-123, src/range/mod.rs:48-62) are proved as ONE grouped call per run of
-equal-sized sub-proofs (host_range.inc: prove_policy_device, RangeArgs::sub_k), and large batches of short lists are swept
+equal-sized sub-proofs (host_policy.inc: prove_policy_device, RangeArgs::sub_k), and large batches of short lists are swept
 generator-stationary with two lookups per term (k_rp_msm_gs_hi).  Bytes must not move: against the C oracle sub-proof by sub-proof
 (same stream, same first slot), against the ungrouped path, and under every arrangement of the sweep."""
 import ctypes
