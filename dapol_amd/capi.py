@@ -121,6 +121,14 @@ _SIG = {
     "dapol_reprove_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
     "dapol_reprove_entities_shared": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P,
                                                        _P, _P]),
+    "dapol_proof_store_create": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.POINTER(_P)]),
+    "dapol_proof_store_destroy": (ctypes.c_int32, [_P]),
+    "dapol_proof_store_refresh": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P, _P]),
+    "dapol_proof_store_rows": (ctypes.c_size_t, [_P]),
+    "dapol_proof_store_entity_bytes": (ctypes.c_size_t, [_P]),
+    "dapol_proof_store_fetch": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
+    "dapol_proof_store_read": (ctypes.c_int32, [_P, ctypes.c_size_t, ctypes.c_size_t, _P, _P, _P, _P]),
+    "dapol_proof_store_verify": (ctypes.c_int32, [_P, _P, _P]),
     "dapol_workload_create": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_create_shard": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_build": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(WorkloadStats)]),
@@ -656,8 +664,9 @@ class Tree:
             _chk(lib().dapol_tree_build(ctx.h, height, n, _ptr(leaf_idx), _ptr(v), _ptr(r32), _ptr(seed), int(enforce_sparsity), ctypes.byref(self.h)))
 
     def close(self):
+        """dapol_tree_destroy.  A tree with an open ProofStore is not destroyed: DapolError, and the handle stays."""
         if self.h:
-            lib().dapol_tree_destroy(self.h)
+            _chk(lib().dapol_tree_destroy(self.h))
             self.h = _P()
 
     def __del__(self):
@@ -798,6 +807,74 @@ class Tree:
         _chk(lib().dapol_reprove_entities_shared(self.ctx.h, self.h, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(seed), _ptr(has_old),
                                                  _ptr(oC), _ptr(oR), _ptr(C), _ptr(H), _ptr(out), ctypes.byref(proved), ctypes.byref(kept)))
         return C, H, out, int(proved.value), int(kept.value)
+
+
+class ProofStore:
+    """dapol_proof_store: the proofs of prove_entities_shared for one (tree, policy, aggregation factor, n_bits, nonce seed), resident in
+    HBM and re-proved in place after edits of the tree.  Keeps a reference to its Tree (which cannot be closed while the store is open)."""
+
+    def __init__(self, tree, policy, aggregation_factor, n_bits, nonce_seed):
+        self.tree, self.ctx = tree, tree.ctx
+        seed = _u8(np.frombuffer(nonce_seed, np.uint8))
+        self.h = _P()
+        _chk(lib().dapol_proof_store_create(tree.ctx.h, tree.h, policy, aggregation_factor, n_bits, _ptr(seed), ctypes.byref(self.h)))
+        self.H = tree.height
+        self.entity_bytes = int(lib().dapol_proof_store_entity_bytes(self.h))
+
+    def close(self):
+        if self.h:
+            lib().dapol_proof_store_destroy(self.h)
+            self.h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def rows(self):
+        return int(lib().dapol_proof_store_rows(self.h))
+
+    def refresh(self, leaf_idx=None):
+        """Makes the store hold the shared call's proofs of leaf_idx (strictly increasing; None: every leaf of the tree; an empty list
+        empties it) for the tree as it is now.  Returns (proved, kept, moved_rows)."""
+        proved, kept, moved = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if leaf_idx is None:
+            b, ptr = 0, None
+        else:
+            leaf_idx = _u64(leaf_idx)
+            b = leaf_idx.shape[0]
+            ptr = _ptr(leaf_idx if b else np.zeros(1, np.uint64))          # (a pointer even for no rows: NULL means every leaf)
+        _chk(lib().dapol_proof_store_refresh(self.h, b, ptr, ctypes.byref(proved), ctypes.byref(kept), ctypes.byref(moved)))
+        return int(proved.value), int(kept.value), int(moved.value)
+
+    def _out(self, n):
+        return (np.zeros((n, self.H, 32), np.uint8), np.zeros((n, self.H, self.ctx.hb), np.uint8), np.zeros((n, max(self.entity_bytes, 1)), np.uint8))
+
+    def fetch(self, leaf_idx):
+        """The rows of the given leaves (any order, duplicates allowed): (found, path_C, path_H, blobs); zero rows where found == 0."""
+        leaf_idx = _u64(leaf_idx)
+        k = leaf_idx.shape[0]
+        found = np.zeros(k, np.uint8)
+        C, H, out = self._out(k)
+        _chk(lib().dapol_proof_store_fetch(self.h, k, _ptr(leaf_idx) if k else None, _ptr(found), _ptr(C), _ptr(H), _ptr(out)))
+        return found, C, H, out
+
+    def read(self, first=0, count=None):
+        """Rows [first, first + count) (count None: to the end): (leaf_idx, path_C, path_H, blobs)."""
+        count = self.rows - first if count is None else count
+        idx = np.zeros(max(count, 0), np.uint64)
+        C, H, out = self._out(max(count, 0))
+        _chk(lib().dapol_proof_store_read(self.h, first, count, _ptr(idx), _ptr(C), _ptr(H), _ptr(out)))
+        return idx, C, H, out
+
+    def verify(self, verify_seed=None):
+        """verify_entities' verdicts for every row against the tree as it is now; only the verdict bytes leave the device."""
+        ok = np.zeros(self.rows, np.uint8)
+        seed = _u8(np.frombuffer(verify_seed, np.uint8)) if verify_seed is not None else None   # None: the library draws one from the OS
+        _chk(lib().dapol_proof_store_verify(self.h, _ptr(seed), _ptr(ok) if ok.shape[0] else None))
+        return ok
 
 
 class Workload:

@@ -21,6 +21,7 @@
 #include "kernels_shared.h"
 #include "kernels_verify_shared.h"
 #include "kernels_reprove.h"
+#include "kernels_store.h"
 
 using namespace dapol;
 
@@ -454,6 +455,7 @@ int32_t dapol_commit_hash_batch(dapol_ctx* ctx, size_t n, const uint64_t* v, con
 #include "host_reprove.inc"
 #include "host_verify.inc"
 #include "host_verify_shared.inc"
+#include "host_store.inc"
 #include "host_leaf.inc"
 #include "host_wire.inc"
 #include "host_batch.inc"

@@ -20,6 +20,14 @@ static LevelView level_view_of(const LevelBuf& L, int t, uint64_t* leaf_idx, uin
     return lv;
 }
 
+// Proof stores (host_store.inc) that live on a tree.  The count belongs to the HANDLE: a rebuild move-assigns a fresh tree over this one
+// (host_tree_edit.inc), and assignment leaves the count where it is.
+struct StoreCount {
+    int n = 0;
+    StoreCount() = default;
+    StoreCount(const StoreCount&) {}
+    StoreCount& operator=(const StoreCount&) { return *this; }
+};
 struct dapol_tree {
     dapol_ctx* ctx = nullptr;
     int height = 0;
@@ -38,6 +46,7 @@ struct dapol_tree {
     DevBuf<uint32_t> wide;
     std::vector<WideView> wviews;      // host copy: pointers into `wide`
     DevBuf<WideView> d_wviews;
+    StoreCount stores;                 // live dapol_proof_store objects on this tree: dapol_tree_destroy refuses while there is one
     LevelView view(int k, int32_t* ext = nullptr) { LevelView lv = level_view_of(levels[k], k, leaf_idx, leaf_v, leaf_r); lv.ext = ext; return lv; }
     std::vector<LevelView> views() { std::vector<LevelView> hv; for (int k = 0; k <= height; k++) hv.push_back(view(k)); return hv; }
 };
@@ -363,6 +372,7 @@ int32_t dapol_tree_build_shard(dapol_ctx* ctx, int32_t total_height, int32_t sha
 
 int32_t dapol_tree_destroy(dapol_tree* tree) {
     if (!tree) return DAPOL_OK;
+    if (tree->stores.n > 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "the tree still has a proof store: destroy the store first (nothing was destroyed)");
     dapol_tree_owned* own = static_cast<dapol_tree_owned*>(tree);
     dapol_ctx* ctx = own->holds_ctx ? tree->ctx : nullptr;
     if (tree->ctx) (void)hipSetDevice(tree->ctx->device);

@@ -259,6 +259,82 @@ struct DapolOptions {
                                       // sets it: a known seed makes every padding blinding publicly derivable (node.rs:86-88)
 };
 
+// dapol_proof_store: the proofs of Dapol::generate_proofs_shared kept on the GPU and re-proved in place after update / insert / remove
+// (Dapol::proof_store makes one).  Move-only.  It shares ownership of the tree it was made on, and its destructor destroys the store
+// before that share is dropped, so the tree outlives the store whatever becomes of the Dapol.
+class ProofStore {
+  public:
+    ProofStore(ProofStore&& o) noexcept { *this = std::move(o); }
+    ProofStore& operator=(ProofStore&& o) noexcept {
+        if (this != &o) {
+            reset();
+            h_ = o.h_; o.h_ = nullptr;
+            ctx_ = std::move(o.ctx_); tree_ = std::move(o.tree_);
+            height_ = o.height_; aggregation_factor_ = o.aggregation_factor_; policy_ = o.policy_; n_bits_ = o.n_bits_;
+        }
+        return *this;
+    }
+    ProofStore(const ProofStore&) = delete;
+    ProofStore& operator=(const ProofStore&) = delete;
+    ~ProofStore() { reset(); }
+    struct Refreshed { uint64_t proved = 0, kept = 0, moved_rows = 0; };
+    // every leaf of the tree as it is now
+    Refreshed refresh() { return refresh_impl(0, nullptr); }
+    // the given leaves, strictly increasing (none: the store is emptied)
+    Refreshed refresh(const std::vector<uint64_t>& leaves) {
+        static const uint64_t none = 0;
+        return refresh_impl(leaves.size(), leaves.empty() ? &none : leaves.data());
+    }
+    size_t rows() const { return dapol_proof_store_rows(h_); }
+    // The stored proof of one leaf; None for a leaf the store does not hold.
+    std::optional<DapolProof> proof(uint64_t leaf) const {
+        auto v = proofs({leaf});
+        return std::move(v[0]);
+    }
+    std::vector<std::optional<DapolProof>> proofs(const std::vector<uint64_t>& leaves) const {
+        const size_t k = leaves.size(), h = (size_t)height_, es = dapol_proof_store_entity_bytes(h_);
+        std::vector<uint8_t> found(k + 1, 0), C(k * h * 32 + 1), H(k * h * 32 + 1), R(k * es + 1);
+        check(dapol_proof_store_fetch(h_, k, leaves.data(), found.data(), C.data(), H.data(), R.data()));
+        std::vector<std::optional<DapolProof>> out(k);
+        for (size_t e = 0; e < k; e++) {
+            if (!found[e]) continue;
+            DapolProof p;
+            p.leaf_index = leaves[e];
+            p.merkle_siblings.resize(h);
+            for (size_t s = 0; s < h; s++) {
+                std::memcpy(p.merkle_siblings[s].com.data(), &C[(e * h + s) * 32], 32);
+                std::memcpy(p.merkle_siblings[s].hash.data(), &H[(e * h + s) * 32], 32);
+            }
+            p.range_proofs.assign(R.begin() + e * es, R.begin() + (e + 1) * es);
+            p.policy = policy_; p.aggregation_factor = aggregation_factor_; p.n_bits = n_bits_; p.height = height_;
+            out[e] = std::move(p);
+        }
+        return out;
+    }
+    // DapolProof::verify of every row against the tree as it is now, on the device: true when the store is not empty and every row verifies.
+    bool verify() const {
+        const size_t n = rows();
+        std::vector<uint8_t> ok(n + 1, 0);
+        check(dapol_proof_store_verify(h_, nullptr, ok.data()));
+        return n > 0 && std::all_of(ok.begin(), ok.begin() + n, [](uint8_t x) { return x != 0; });
+    }
+  private:
+    friend class Dapol;
+    ProofStore() = default;
+    void reset() { if (h_) dapol_proof_store_destroy(h_); h_ = nullptr; tree_.reset(); ctx_.reset(); }
+    Refreshed refresh_impl(size_t b, const uint64_t* idx) {
+        Refreshed r;
+        check(dapol_proof_store_refresh(h_, b, idx, &r.proved, &r.kept, &r.moved_rows));
+        return r;
+    }
+    dapol_proof_store* h_ = nullptr;
+    std::shared_ptr<Context> ctx_;
+    std::shared_ptr<dapol_tree> tree_;
+    int height_ = 0, n_bits_ = 64;
+    size_t aggregation_factor_ = 0;
+    Policy policy_ = Policy::Padding;
+};
+
 // Dapol<D, R> (src/dapol/mod.rs:78-83)
 class Dapol {
   public:
@@ -466,6 +542,15 @@ class Dapol {
         if (rc == DAPOL_ERR_UNKNOWN_LEAF) return std::nullopt;
         check(rc);
         return std::make_pair(unpack(leaves, C, H, R, es, n_bits), proved);
+    }
+    // An empty device-resident store of this tree's shared proofs under nonce_seed (dapol_proof_store_create): refresh() fills it and
+    // brings it up to date after edits, proof(leaf) serves from it.  The tree must have been built.
+    ProofStore proof_store(const Bytes32& nonce_seed, int n_bits = 64) const {
+        ProofStore st;
+        check(dapol_proof_store_create(ctx_->get(), tree_.get(), (int)policy_, (int)aggregation_factor_, n_bits, nonce_seed.data(), &st.h_));
+        st.ctx_ = ctx_; st.tree_ = tree_;
+        st.height_ = height_; st.aggregation_factor_ = aggregation_factor_; st.policy_ = policy_; st.n_bits_ = n_bits;
+        return st;
     }
     // Verifies many single-leaf proofs in one call with every run of equal sub-proofs checked once (dapol_verify_entities_shared):
     // a verdict per proof -- the ones DapolProof::verify gives one by one -- and the number of range proofs actually checked.  Proofs

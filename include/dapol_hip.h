@@ -375,6 +375,61 @@ int32_t dapol_reprove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b
                                       const uint8_t* old_path_C32, const uint8_t* old_range, uint8_t* path_C32, uint8_t* path_H32,
                                       uint8_t* range_out, uint64_t* proved_out, uint64_t* kept_out);
 
+/* A PROOF STORE keeps what dapol_prove_entities_shared issues -- for one (context, tree, policy, aggregation factor, n_bits, nonce seed) --
+ * in device memory between calls: the strictly increasing leaf indexes of its rows, their sibling commitments [rows][H][32] and hashes
+ * [rows][H][dapol_ctx_digest_bytes], their blobs [rows][dapol_entity_proof_size], exactly the shared call's layout.  After an edit of the
+ * tree a refresh re-proves what dapol_reprove_entities_shared would re-prove, with the old data where the last refresh left it: no
+ * old array goes up and no blob comes down; a caller fetches the rows it serves.  PLAIN TREES ONLY, no tape mode, as the re-prover.
+ *   Ownership.  The store retains its context and is counted by its tree: dapol_tree_destroy on a tree with a live store returns
+ * DAPOL_ERR_INVALID_ARGUMENT and destroys nothing -- destroy the store first.  The tree may be edited freely between calls (update,
+ * insert, remove, whichever path they take); the store reads it only inside its own calls, on the context's stream, so calls on one
+ * context must not run concurrently, as everywhere.  Every call below except _destroy refuses (DAPOL_ERR_INVALID_ARGUMENT, nothing
+ * written) a NULL store, a tree marked invalid, a store marked unusable, and a dapol_wire_config whose siblings_leaf_first differs
+ * from the value recorded at creation (the stored paths and the plan's keys are in that order).
+ *   dapol_proof_store_create: an empty store (0 rows).  Refuses what dapol_reprove_entities_shared refuses for the same context, tree,
+ * policy, aggregation_factor and n_bits, with the same codes, messages and precedence, and a tree that does not own its leaves (a
+ * workload's), as dapol_tree_update does.  *store is written only on success.
+ *   dapol_proof_store_destroy: overwrites the seed on the device, frees everything, releases the context.  NULL is DAPOL_OK.
+ *   dapol_proof_store_refresh: afterwards the store holds the shared call's outputs, for the tree as it is now, of the b strictly
+ * increasing leaf_idx.  leaf_idx = NULL with b = 0: every leaf of the tree, read from the tree's own device array (no upload); a
+ * non-NULL leaf_idx with b = 0 empties the store.  *proved = heads and *kept = (sub-proof, row) pairs not dirty, as
+ * dapol_reprove_entities_shared defines them with the store's previous rows as the old data; *moved_rows = old rows copied into new
+ * buffers.  Each of the three may be NULL.  When the leaf set is unchanged -- every update-only edit -- nothing moves (*moved_rows = 0):
+ * the new paths are gathered into the store's spare sibling arrays and compared with the ones in use, the dirty pieces are written
+ * into the blobs where they lie, the arrays swap.  Otherwise the surviving rows are copied into newly allocated buffers
+ * (*moved_rows = their number; the old blob buffer is freed after the copy, so both exist for the length of the call), new leaves are
+ * proved from scratch.  All or nothing up to the first write into the store: non-increasing indexes, an index that is no leaf
+ * (DAPOL_ERR_UNKNOWN_LEAF) and a failed allocation (DAPOL_ERR_OUT_OF_MEMORY) leave the store byte for byte as it was; when rows
+ * move every write goes to the new buffers, so any failure does.  A HIP failure after the first write of an in-place refresh marks
+ * the store unusable, the way trees are marked: destroy it and create it again.
+ *   dapol_proof_store_rows / _entity_bytes: the row count; dapol_entity_proof_size of the store's shape.  0 for NULL.
+ *   dapol_proof_store_fetch: the rows of k leaves, in any order, duplicates allowed, gathered on the device into one staging buffer and
+ * copied back from there: found[i] = 1 and row i of path_C32 [k][H][32], path_H32 [k][H][digest bytes], range_out [k][entity bytes]
+ * filled, or found[i] = 0 and the rows zero for a leaf the store does not hold (whether or not the tree has it).  Output pointers may
+ * be NULL.  k = 0 does nothing.
+ *   dapol_proof_store_read: rows [first, first + count) by plain copies, leaf indexes included; refused when first + count exceeds
+ * the rows.  Output pointers may be NULL.
+ *   dapol_proof_store_verify: ok[rows] = what dapol_verify_entities returns for the rows read back, with the leaves' own commitments and
+ * hashes and the root taken from the tree as it is now -- so in a store that has not been refreshed since an edit every row whose path
+ * passes an edited leaf fails (all but a lone edited leaf's own row: its edit lies below none of its own siblings), which is the point
+ * of the check.  Only the verdict bytes cross the bus.  verify_seed32 = NULL draws one, as elsewhere.  A stored leaf that the
+ * tree no longer holds -> DAPOL_ERR_UNKNOWN_LEAF, nothing written.
+ *   When to use it (tools/bench_proof_store.py): whenever proofs are served after edits and the caller does not
+ * need every blob back after every edit. */
+typedef struct dapol_proof_store dapol_proof_store;
+int32_t dapol_proof_store_create(dapol_ctx* ctx, dapol_tree* tree, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                                 const uint8_t nonce_seed32[32], dapol_proof_store** store);
+int32_t dapol_proof_store_destroy(dapol_proof_store* store);
+int32_t dapol_proof_store_refresh(dapol_proof_store* store, size_t b, const uint64_t* leaf_idx, uint64_t* proved, uint64_t* kept,
+                                  uint64_t* moved_rows);
+size_t dapol_proof_store_rows(dapol_proof_store* store);
+size_t dapol_proof_store_entity_bytes(dapol_proof_store* store);
+int32_t dapol_proof_store_fetch(dapol_proof_store* store, size_t k, const uint64_t* leaf_idx, uint8_t* found, uint8_t* path_C32,
+                                uint8_t* path_H32, uint8_t* range_out);
+int32_t dapol_proof_store_read(dapol_proof_store* store, size_t first, size_t count, uint64_t* leaf_idx_out, uint8_t* path_C32,
+                               uint8_t* path_H32, uint8_t* range_out);
+int32_t dapol_proof_store_verify(dapol_proof_store* store, const uint8_t verify_seed32[32], uint8_t* ok);
+
 /* Serializable for RangeProofPadding / RangeProofSplitting (src/range/padding.rs:38-69, src/range/splitting.rs:36-84):
  * the range-proof blob of ONE entity as written by dapol_prove_entities <-> R::serialize() bytes
  * ((aggregated_num ||) (size || proof)... || individual_num || proofs...; field widths src/range/mod.rs:18-21).
