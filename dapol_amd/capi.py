@@ -86,6 +86,8 @@ _SIG = {
     "dapol_tree_update": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P]),
     "dapol_tree_remove": (ctypes.c_int32, [_P, ctypes.c_size_t, _P]),
     "dapol_tree_insert": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P]),
+    "dapol_tree_derive_leaves": (ctypes.c_int32, [_P, ctypes.c_int32, _P, ctypes.c_size_t, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dapol_tree_insert_liabilities": (ctypes.c_int32, [_P, ctypes.c_int32, _P, ctypes.c_size_t, ctypes.c_size_t, _P, _P, _P, _P, _P, _P]),
     "dapol_tree_last_update_path": (ctypes.c_int32, [_P, _P]),
     "dapol_diag_fork_guard_waits": (ctypes.c_int32, [_P]),
     "dapol_diag_verify_fallbacks": (ctypes.c_int32, [_P]),
@@ -200,6 +202,22 @@ def _u8(a, *shape):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(_P)
+
+
+def _pack_liabilities(liabilities, audit_seed):
+    """[(internal_id bytes, external_id bytes, value)] -> the C ABI's packed ids: (n, iid, ioff, eid, eoff, values, seed)."""
+    n = len(liabilities)
+    iid = b"".join(l[0] for l in liabilities)
+    eid = b"".join(l[1] for l in liabilities)
+    ioff = np.zeros(n + 1, np.uint32)
+    eoff = np.zeros(n + 1, np.uint32)
+    ioff[1:] = np.cumsum([len(l[0]) for l in liabilities])
+    eoff[1:] = np.cumsum([len(l[1]) for l in liabilities])
+    vals = _u64([l[2] for l in liabilities])
+    ib = _u8(np.frombuffer(iid, np.uint8)) if iid else np.zeros(1, np.uint8)
+    eb = _u8(np.frombuffer(eid, np.uint8)) if eid else np.zeros(1, np.uint8)
+    sd = _u8(np.frombuffer(audit_seed, np.uint8)) if audit_seed else None
+    return n, ib, ioff, eb, eoff, vals, sd
 
 
 def range_proofs_serialize(height, policy, aggregation_factor, n_bits, blob):
@@ -334,17 +352,7 @@ class Context:
     def build_leaf_nodes(self, liabilities, audit_seed, height, digest=DIGEST_BLAKE3):
         """build_leaf_nodes (src/dapol/mod.rs:323-399): liabilities = [(internal_id bytes, external_id bytes, value)] in
         input order -> dict(leaf_idx, v, r (sorted by index), order (input position per sorted leaf), idx_by_entity)."""
-        n = len(liabilities)
-        iid = b"".join(l[0] for l in liabilities)
-        eid = b"".join(l[1] for l in liabilities)
-        ioff = np.zeros(n + 1, np.uint32)
-        eoff = np.zeros(n + 1, np.uint32)
-        ioff[1:] = np.cumsum([len(l[0]) for l in liabilities])
-        eoff[1:] = np.cumsum([len(l[1]) for l in liabilities])
-        vals = _u64([l[2] for l in liabilities])
-        ib = _u8(np.frombuffer(iid, np.uint8)) if iid else np.zeros(1, np.uint8)
-        eb = _u8(np.frombuffer(eid, np.uint8)) if eid else np.zeros(1, np.uint8)
-        sd = _u8(np.frombuffer(audit_seed, np.uint8)) if audit_seed else None
+        n, ib, ioff, eb, eoff, vals, sd = _pack_liabilities(liabilities, audit_seed)
         idx, v, order, by_e = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
         r = np.zeros((n, 32), np.uint8)
         _chk(lib().dapol_build_leaf_nodes(self.h, digest, _ptr(sd), len(audit_seed), height, n, _ptr(ib), _ptr(ioff), _ptr(eb), _ptr(eoff),
@@ -696,6 +704,25 @@ class Tree:
         error).  Chains may share nodes: sibling pairs and whole new subtrees go in place too."""
         leaf_idx, v, r32 = _u64(leaf_idx), _u64(v), _u8(r32)
         _chk(lib().dapol_tree_insert(self.h, leaf_idx.shape[0], _ptr(leaf_idx), _ptr(v), _ptr(r32)))
+
+    def derive_leaves(self, liabilities, audit_seed, digest=DIGEST_BLAKE3):
+        """dapol_tree_derive_leaves: build_leaf_nodes for liabilities [(internal_id bytes, external_id bytes, value)] that JOIN this
+        tree -- an index that is a leaf now is taken.  Nothing is written; the result is build_leaf_nodes' dict for the batch."""
+        n, ib, ioff, eb, eoff, vals, sd = _pack_liabilities(liabilities, audit_seed)
+        idx, v, order, by_e = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        r = np.zeros((n, 32), np.uint8)
+        _chk(lib().dapol_tree_derive_leaves(self.h, digest, _ptr(sd), len(audit_seed), n, _ptr(ib), _ptr(ioff), _ptr(eb), _ptr(eoff), _ptr(vals),
+                                            _ptr(idx), _ptr(v), _ptr(r), _ptr(order), _ptr(by_e)))
+        return dict(leaf_idx=idx, v=v, r=r, order=order, idx_by_entity=by_e)
+
+    def insert_liabilities(self, liabilities, audit_seed, digest=DIGEST_BLAKE3):
+        """dapol_tree_insert_liabilities: derive_leaves, then insert of the result (all or nothing).  Returns idx_by_entity: where each
+        new liability went.  The tree holds no ids: the caller checks that none of the internal ids is in the tree already."""
+        n, ib, ioff, eb, eoff, vals, sd = _pack_liabilities(liabilities, audit_seed)
+        by_e = np.zeros(n, np.uint64)
+        _chk(lib().dapol_tree_insert_liabilities(self.h, digest, _ptr(sd), len(audit_seed), n, _ptr(ib), _ptr(ioff), _ptr(eb), _ptr(eoff), _ptr(vals),
+                                                 _ptr(by_e)))
+        return by_e
 
     def last_update_path(self):
         """What the last update, insert or removal did: 0 = rebuilt the tree, 1 = replaced in place, 2 = inserted in place (disjoint

@@ -22,17 +22,19 @@ __global__ void k_leaf_gather(size_t n, const uint32_t* ord, const uint64_t* val
     for (int i = 0; i < 8; i++) r_sorted[p * 8 + i] = blind[(size_t)e * 8 + i];
 }
 
-int32_t dapol_build_leaf_nodes(dapol_ctx* ctx, int32_t digest_id, const uint8_t* audit_seed, size_t audit_seed_len, int32_t height, size_t n,
-                               const uint8_t* internal_ids, const uint32_t* internal_off, const uint8_t* external_ids,
-                               const uint32_t* external_off, const uint64_t* values, uint64_t* leaf_idx_sorted, uint64_t* v_sorted,
-                               uint8_t* r32_sorted, uint32_t* order_sorted, uint64_t* idx_by_entity) {
+// build_leaf_nodes over n liabilities that join the leaves O (none for dapol_build_leaf_nodes): a candidate that is one of O is taken
+// before the batch starts (kernels_leaf.h, LeafOccupied); the sparsity rule of Dapol::new counts O's leaves too.
+static int32_t leaf_derive(dapol_ctx* ctx, int32_t digest_id, const uint8_t* audit_seed, size_t audit_seed_len, int32_t height, size_t n,
+                           const uint8_t* internal_ids, const uint32_t* internal_off, const uint8_t* external_ids, const uint32_t* external_off,
+                           const uint64_t* values, uint64_t* leaf_idx_sorted, uint64_t* v_sorted, uint8_t* r32_sorted, uint32_t* order_sorted,
+                           uint64_t* idx_by_entity, LeafOccupied O) {
     if (!ctx || !n || !internal_off || !external_off || !values || !leaf_idx_sorted || !v_sorted || !r32_sorted || !order_sorted ||
         (audit_seed_len && !audit_seed))
         return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
     if (digest_id != DAPOL_DIGEST_BLAKE3 && digest_id != DAPOL_DIGEST_BLAKE2S) return fail(DAPOL_ERR_INVALID_DIGEST_SIZE, "digest must be BLAKE3 or Blake2s (32 bytes)");
     if (height > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
     if (height < 1) return fail(DAPOL_ERR_INVALID_ARGUMENT, "tree height must be at least 1");
-    if (height < 64 && (double)n * 2.0 > (double)(1ull << height)) return fail(DAPOL_ERR_SPARSITY_TOO_SMALL, "2^height < 2 * number of liabilities");
+    if (height < 64 && (double)(n + O.n) * 2.0 > (double)(1ull << height)) return fail(DAPOL_ERR_SPARSITY_TOO_SMALL, "2^height < 2 * number of liabilities");
     if (n > ((size_t)1 << 31) || audit_seed_len > 512) return fail(DAPOL_ERR_INVALID_ARGUMENT, "at most 2^31 liabilities; audit seed at most 512 bytes");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -84,11 +86,15 @@ int32_t dapol_build_leaf_nodes(dapol_ctx* ctx, int32_t digest_id, const uint8_t*
         HIPCHK(hipMemsetAsync(tflags.p, 0, 8, st));
         HIPCHK(hipMemsetAsync(err.p + 3, 0xff, 4, st));                        // (atomicMin target: the earliest entity that cannot be mapped)
         LeafTable T{tkey.p, towner.p, (uint32_t)(tsz - 1), tpos.p, ttries.p, tflags.p};
-        hipLaunchKernelGGL(k_leaf_claim_first, dim3(nblk(n, 256)), dim3(256), 0, st, A, T); LAUNCH_CHECK();
+        if (O.n) hipLaunchKernelGGL(k_leaf_claim_first_onto, dim3(nblk(n, 256)), dim3(256), 0, st, A, T, O);
+        else hipLaunchKernelGGL(k_leaf_claim_first, dim3(nblk(n, 256)), dim3(256), 0, st, A, T);
+        LAUNCH_CHECK();
         uint32_t hflags[2] = {1, 0};
         for (int round = 0; round < 100000 && hflags[0] && !hflags[1]; round++) {
             HIPCHK(hipMemsetAsync(tflags.p, 0, 4, st));
-            hipLaunchKernelGGL(k_leaf_settle, dim3(nblk(n, 256)), dim3(256), 0, st, A, T); LAUNCH_CHECK();
+            if (O.n) hipLaunchKernelGGL(k_leaf_settle_onto, dim3(nblk(n, 256)), dim3(256), 0, st, A, T, O);
+            else hipLaunchKernelGGL(k_leaf_settle, dim3(nblk(n, 256)), dim3(256), 0, st, A, T);
+            LAUNCH_CHECK();
             HIPCHK(hipMemcpyAsync(hflags, tflags.p, 8, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
         }
@@ -114,7 +120,9 @@ int32_t dapol_build_leaf_nodes(dapol_ctx* ctx, int32_t digest_id, const uint8_t*
     // the one-lane path: first candidates sorted by (index, input order) -- radix sort is stable -- then the losers in input order
     HIPCHK(losers.alloc(n)); HIPCHK(nl.alloc(1));
     HIPCHK(hipMemsetAsync(nl.p, 0, 4, st));
-    hipLaunchKernelGGL(k_leaf_mark, dim3(nblk(n, 256)), dim3(256), 0, st, n, key2.p, ord2.p, losers.p, nl.p); LAUNCH_CHECK();
+    if (O.n) hipLaunchKernelGGL(k_leaf_mark_onto, dim3(nblk(n, 256)), dim3(256), 0, st, n, key2.p, ord2.p, losers.p, nl.p, O);
+    else hipLaunchKernelGGL(k_leaf_mark, dim3(nblk(n, 256)), dim3(256), 0, st, n, key2.p, ord2.p, losers.p, nl.p);
+    LAUNCH_CHECK();
     uint32_t n_losers = 0;
     HIPCHK(hipMemcpyAsync(&n_losers, nl.p, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -127,6 +135,7 @@ int32_t dapol_build_leaf_nodes(dapol_ctx* ctx, int32_t digest_id, const uint8_t*
         LeafResolve R{};
         R.n = n; R.skey = key2.p; R.sord = ord2.p; R.heap = losers.p; R.heap_n = n_losers; R.evicted = evicted.p;
         R.tab_key = tab_key.p; R.tab_used = tab_used.p; R.tab_mask = (uint32_t)(tsz - 1);
+        R.occ = O;
         hipLaunchKernelGGL(k_leaf_resolve, dim3(1), dim3(64), 0, st, A, R); LAUNCH_CHECK();
         HIPCHK(hipMemcpyAsync(herr, err.p, 16, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -148,4 +157,56 @@ int32_t dapol_build_leaf_nodes(dapol_ctx* ctx, int32_t digest_id, const uint8_t*
     if (idx_by_entity) HIPCHK(hipMemcpyAsync(idx_by_entity, cand.p, n * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return DAPOL_OK;
+}
+
+int32_t dapol_build_leaf_nodes(dapol_ctx* ctx, int32_t digest_id, const uint8_t* audit_seed, size_t audit_seed_len, int32_t height, size_t n,
+                               const uint8_t* internal_ids, const uint32_t* internal_off, const uint8_t* external_ids,
+                               const uint32_t* external_off, const uint64_t* values, uint64_t* leaf_idx_sorted, uint64_t* v_sorted,
+                               uint8_t* r32_sorted, uint32_t* order_sorted, uint64_t* idx_by_entity) {
+    return leaf_derive(ctx, digest_id, audit_seed, audit_seed_len, height, n, internal_ids, internal_off, external_ids, external_off, values,
+                       leaf_idx_sorted, v_sorted, r32_sorted, order_sorted, idx_by_entity, LeafOccupied{nullptr, 0});
+}
+
+// What both id-based inserts refuse about the tree before anything else: the occupied set is the tree's own level-0 index array, so
+// the tree must hold ALL the leaves its liabilities compete with.
+static int32_t leaf_join_begin(dapol_tree* tree) {
+    TREE_USABLE(tree);
+    if (tree->shard_bits)
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "a shard tree holds only its shard's leaves, not the whole set of taken indexes: derive the leaves against the whole tree");
+    return DAPOL_OK;
+}
+int32_t dapol_tree_derive_leaves(dapol_tree* tree, int32_t digest_id, const uint8_t* audit_seed, size_t audit_seed_len, size_t k,
+                                 const uint8_t* internal_ids, const uint32_t* internal_off, const uint8_t* external_ids,
+                                 const uint32_t* external_off, const uint64_t* values, uint64_t* leaf_idx_sorted, uint64_t* v_sorted,
+                                 uint8_t* r32_sorted, uint32_t* order_sorted, uint64_t* idx_by_entity) {
+    if (!tree || (audit_seed_len && !audit_seed) ||
+        (k && (!internal_off || !external_off || !values || !leaf_idx_sorted || !v_sorted || !r32_sorted || !order_sorted)))
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return DAPOL_OK;
+    int32_t rc = leaf_join_begin(tree);
+    if (rc) return rc;
+    return leaf_derive(tree->ctx, digest_id, audit_seed, audit_seed_len, tree->index_bits, k, internal_ids, internal_off, external_ids, external_off, values,
+                       leaf_idx_sorted, v_sorted, r32_sorted, order_sorted, idx_by_entity, LeafOccupied{tree->leaf_idx, tree->levels[0].n});
+}
+int32_t dapol_tree_insert_liabilities(dapol_tree* tree, int32_t digest_id, const uint8_t* audit_seed, size_t audit_seed_len, size_t k,
+                                      const uint8_t* internal_ids, const uint32_t* internal_off, const uint8_t* external_ids,
+                                      const uint32_t* external_off, const uint64_t* values, uint64_t* idx_by_entity) {
+    if (!tree || (audit_seed_len && !audit_seed) || (k && (!internal_off || !external_off || !values))) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return DAPOL_OK;
+    int32_t rc = leaf_join_begin(tree);
+    if (rc) return rc;
+    dapol_tree_owned* own = nullptr;
+    rc = tree_edit_begin(tree, "an insert", &own);
+    if (rc) return rc;
+    if (k > ((size_t)1 << 31)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "at most 2^31 liabilities; audit seed at most 512 bytes");
+    // the derived batch, k x 48 bytes, comes to the host and goes into the insert as any caller's would
+    std::vector<uint64_t> idx(k), v(k), by_entity(k);
+    std::vector<uint8_t> r(k * 32);
+    std::vector<uint32_t> order(k);
+    rc = leaf_derive(tree->ctx, digest_id, audit_seed, audit_seed_len, tree->index_bits, k, internal_ids, internal_off, external_ids, external_off, values,
+                     idx.data(), v.data(), r.data(), order.data(), by_entity.data(), LeafOccupied{tree->leaf_idx, tree->levels[0].n});
+    if (rc) return rc;
+    rc = tree_edit_end(tree, tree_insert_impl(own, k, idx.data(), v.data(), r.data()));
+    if (rc == DAPOL_OK && idx_by_entity) memcpy(idx_by_entity, by_entity.data(), k * 8);
+    return rc;
 }

@@ -41,6 +41,20 @@ __device__ __forceinline__ uint64_t leaf_index_of(const uint32_t* st, int height
     return be >> (64 - height);
 }
 
+// The leaves a batch JOINS (dapol_tree_derive_leaves): the tree's level-0 index array as it lies in HBM, sorted, strictly increasing.
+// A candidate found here counts as owned by an entity earlier than every entity of the batch: it holds its slot for good, so the
+// fixed-point argument above covers it unchanged.  It is looked up (log2 n reads), never put into the slot table, which stays sized
+// by the batch.  n = 0: nothing is occupied (dapol_build_leaf_nodes).
+struct LeafOccupied {
+    const uint64_t* idx;
+    size_t n;
+};
+__device__ __forceinline__ bool leaf_occupied(const LeafOccupied& O, uint64_t x) {
+    size_t lo = 0, hi = O.n;
+    while (lo < hi) { size_t mid = (lo + hi) >> 1; if (O.idx[mid] < x) lo = mid + 1; else hi = mid; }
+    return lo < O.n && O.idx[lo] == x;
+}
+
 __global__ __launch_bounds__(64) void k_leaf_hash(LeafArgs A) {
     size_t e = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (e >= A.n) return;
@@ -105,6 +119,15 @@ __global__ void k_leaf_mark(size_t n, const uint64_t* skey, const uint32_t* sord
     losers[k] = sord[p];
 }
 
+// The same for a batch that joins a tree: an entity whose first candidate is a current leaf never holds it, first of its group or not.
+__global__ void k_leaf_mark_onto(size_t n, const uint64_t* skey, const uint32_t* sord, uint32_t* losers, uint32_t* n_losers, LeafOccupied O) {
+    size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (!((p > 0 && skey[p] == skey[p - 1]) || leaf_occupied(O, skey[p]))) return;
+    uint32_t k = atomicAdd(n_losers, 1u);
+    losers[k] = sord[p];
+}
+
 struct LeafResolve {
     size_t n;
     const uint64_t* skey;      // [n] sorted first candidates
@@ -115,6 +138,7 @@ struct LeafResolve {
     uint64_t* tab_key;         // open-addressing set of slots taken by resolved colliders
     uint8_t* tab_used;
     uint32_t tab_mask;
+    LeafOccupied occ;          // the leaves the batch joins (n = 0: none)
 };
 __device__ inline void heap_push(uint32_t* h, uint32_t& n, uint32_t v) {
     uint32_t i = n++;
@@ -159,6 +183,8 @@ __global__ void k_leaf_resolve(LeafArgs A, LeafResolve R) {
             dg_update_words(d, st, 8);
             dg_final(d, st);
             uint64_t x = leaf_index_of(st, A.height);
+            // a current leaf of the tree the batch joins: taken by an entity earlier than all of the batch
+            if (leaf_occupied(R.occ, x)) continue;
             // (a) slot taken by an already resolved collider (all of them precede e)
             bool taken = false;
             uint32_t hp = (uint32_t)((x * 0x9E3779B97F4A7C15ull) >> 32) & R.tab_mask;
@@ -245,6 +271,52 @@ __global__ void k_leaf_settle(LeafArgs A, LeafTable T) {
         const uint32_t prev = leaf_claim(T, x, (uint32_t)e, hp);
         if (T.flags[1]) break;
         if (prev > (uint32_t)e) break;               // ours (until an earlier entity comes for it)
+    }
+    for (int i = 0; i < 8; i++) A.idx_state[e * 8 + i] = st[i];
+    A.cand[e] = x;
+    T.pos[e] = hp;
+    T.tries[e] = tries;
+    T.flags[0] = 1;
+}
+
+// The same pair for a batch that JOINS a tree (dapol_tree_derive_leaves): every candidate is looked up among the tree's leaves (O)
+// before the slot table sees it.  A hit is a slot held for good by an entity earlier than all of the batch, so the entity draws its
+// next candidate and holds nothing meanwhile (T.pos = LEAF_NO_POS); the table stays sized by the batch.
+#define LEAF_NO_POS 0xFFFFFFFFu
+__global__ void k_leaf_claim_first_onto(LeafArgs A, LeafTable T, LeafOccupied O) {
+    size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= A.n) return;
+    uint32_t hp = LEAF_NO_POS;
+    if (!leaf_occupied(O, A.cand[e])) (void)leaf_claim(T, A.cand[e], (uint32_t)e, hp);
+    T.pos[e] = hp;
+    T.tries[e] = 1;
+}
+__global__ void k_leaf_settle_onto(LeafArgs A, LeafTable T, LeafOccupied O) {
+    size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= A.n) return;
+    uint32_t tries = T.tries[e];
+    if (tries > (uint32_t)A.max_tries) return;       // parked, as in k_leaf_settle
+    uint32_t st[8], hp = T.pos[e];
+    if (hp != LEAF_NO_POS && T.owner[hp] == (uint32_t)e) return;
+    for (int i = 0; i < 8; i++) st[i] = A.idx_state[e * 8 + i];
+    uint64_t x = A.cand[e];
+    for (;;) {
+        if (tries >= (uint32_t)A.max_tries) {        // FailedToMapIndex: parks; err[3] ends as the earliest such position of the batch
+            atomicOr(&A.err[2], 1u);
+            atomicMin(&A.err[3], (uint32_t)e);
+            tries = (uint32_t)A.max_tries + 1;
+            break;
+        }
+        Digest d;
+        dg_init(d, A.kind);
+        dg_update_words(d, st, 8);
+        dg_final(d, st);
+        tries++;
+        x = leaf_index_of(st, A.height);
+        if (leaf_occupied(O, x)) { hp = LEAF_NO_POS; continue; }     // a current leaf: the slot table never sees x
+        const uint32_t prev = leaf_claim(T, x, (uint32_t)e, hp);
+        if (T.flags[1]) break;
+        if (prev > (uint32_t)e) break;
     }
     for (int i = 0; i < 8; i++) A.idx_state[e * 8 + i] = st[i];
     A.cand[e] = x;

@@ -344,27 +344,37 @@ class Dapol {
     static Dapol create(std::shared_ptr<Context> ctx, int digest, const std::vector<Liability>& liabilities, const DapolOptions& options,
                         Policy policy = Policy::Padding) {
         Dapol d = new_blank(std::move(ctx), options.tree_height, options.aggregation_factor, policy);
-        size_t n = liabilities.size();
-        std::vector<uint8_t> iid, eid;
-        std::vector<uint32_t> ioff(n + 1, 0), eoff(n + 1, 0);
-        std::vector<uint64_t> vals(n);
-        for (size_t i = 0; i < n; i++) {
-            iid.insert(iid.end(), liabilities[i].internal_id.begin(), liabilities[i].internal_id.end());
-            eid.insert(eid.end(), liabilities[i].external_id.begin(), liabilities[i].external_id.end());
-            ioff[i + 1] = (uint32_t)iid.size();
-            eoff[i + 1] = (uint32_t)eid.size();
-            vals[i] = liabilities[i].value;
-        }
-        iid.push_back(0); eid.push_back(0);                                 // never pass a null data pointer
+        const size_t n = liabilities.size();
+        const Packed L(liabilities);
         std::vector<uint64_t> idx(n), v(n), by_entity(n);
         std::vector<uint32_t> order(n);
         std::vector<Bytes32> r(n);
-        check(dapol_build_leaf_nodes(d.ctx_->get(), digest, options.audit_seed.data(), options.audit_seed.size(), options.tree_height, n, iid.data(),
-                                     ioff.data(), eid.data(), eoff.data(), vals.data(), idx.data(), v.data(), n ? r[0].data() : nullptr,
+        check(dapol_build_leaf_nodes(d.ctx_->get(), digest, options.audit_seed.data(), options.audit_seed.size(), options.tree_height, n, L.iid.data(),
+                                     L.ioff.data(), L.eid.data(), L.eoff.data(), L.vals.data(), idx.data(), v.data(), n ? r[0].data() : nullptr,
                                      order.data(), by_entity.data()));
         for (size_t i = 0; i < n; i++) d.id_to_idx_map_[liabilities[i].internal_id] = by_entity[i];
         d.build(idx, v, r, options.secret, true);
+        d.digest_ = digest; d.audit_seed_ = options.audit_seed; d.created_ = true;      // what insert_liabilities derives further leaves with
         return d;
+    }
+    // New liabilities join the tree by id (dapol_tree_insert_liabilities): shuffle_index (mod.rs:408-441) with the tree's current leaves
+    // as the indexes already taken, under the digest and the audit seed given to create; then dapol_tree_insert, all or nothing.  With
+    // nothing removed since create, ids map where create over the old and the new liabilities would have put them.  An internal id
+    // that is in id_to_idx_map() already, or given twice, throws DapolError(DAPOL_ERR_DUPLICATED_INTERNAL_ID) before the library is
+    // called (the tree itself holds no ids); the new ids join the map on success only.  A Dapol not made by create has no audit seed:
+    // DapolError(DAPOL_ERR_INVALID_ARGUMENT).
+    void insert_liabilities(const std::vector<Liability>& liabilities) {
+        if (!created_ || !tree_) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        const size_t k = liabilities.size();
+        std::map<LiabilityId, uint64_t> fresh;
+        for (auto& l : liabilities)
+            if (id_to_idx_map_.count(l.internal_id) || !fresh.emplace(l.internal_id, 0).second) throw DapolError(DAPOL_ERR_DUPLICATED_INTERNAL_ID);
+        if (k == 0) return;
+        const Packed L(liabilities);
+        std::vector<uint64_t> by_entity(k);
+        check(dapol_tree_insert_liabilities(tree_.get(), digest_, audit_seed_.data(), audit_seed_.size(), k, L.iid.data(), L.ioff.data(), L.eid.data(),
+                                            L.eoff.data(), L.vals.data(), by_entity.data()));
+        for (size_t i = 0; i < k; i++) id_to_idx_map_[liabilities[i].internal_id] = by_entity[i];
     }
     // Dapol::generate_proof_for_id / generate_proof_batch_for_ids (mod.rs:148-164): None for an unknown id.
     std::optional<DapolProof> generate_proof_for_id(const LiabilityId& id, const Bytes32& nonce_seed, int n_bits = 64) const {
@@ -425,9 +435,8 @@ class Dapol {
     }
     // Adds NEW liabilities at these leaf indexes (dapol_tree_insert; in any order, all or nothing): the tree equals a build over the old
     // and the new leaves with the same seed.  An index that is a leaf already (or given twice) throws
-    // DapolError(DAPOL_ERR_INVALID_ARGUMENT) with nothing inserted.  On a blank Dapol it builds over the whole batch (sorted here; all or nothing too).  There is no insert by
-    // liability id: build_leaf_nodes' collision rule runs over the whole ordered liability list and has no "insert into an existing
-    // set" form.
+    // DapolError(DAPOL_ERR_INVALID_ARGUMENT) with nothing inserted.  On a blank Dapol it builds over the whole batch (sorted here; all or nothing too).  By liability
+    // id: insert_liabilities.
     void insert(const std::vector<uint64_t>& idx, const std::vector<uint64_t>& values, const std::vector<Bytes32>& blindings) {
         insert(idx, values, blindings, tree_ ? Bytes32{} : get_secret());
     }
@@ -625,7 +634,26 @@ class Dapol {
         }
         return out;
     }
+    // liabilities as the C ABI takes them: ids concatenated, with n + 1 offsets
+    struct Packed {
+        std::vector<uint8_t> iid, eid;
+        std::vector<uint32_t> ioff, eoff;
+        std::vector<uint64_t> vals;
+        explicit Packed(const std::vector<Liability>& liabilities) : ioff(liabilities.size() + 1, 0), eoff(liabilities.size() + 1, 0), vals(liabilities.size()) {
+            for (size_t i = 0; i < liabilities.size(); i++) {
+                iid.insert(iid.end(), liabilities[i].internal_id.begin(), liabilities[i].internal_id.end());
+                eid.insert(eid.end(), liabilities[i].external_id.begin(), liabilities[i].external_id.end());
+                ioff[i + 1] = (uint32_t)iid.size();
+                eoff[i + 1] = (uint32_t)eid.size();
+                vals[i] = liabilities[i].value;
+            }
+            iid.push_back(0); eid.push_back(0);                             // never pass a null data pointer
+        }
+    };
     std::map<LiabilityId, uint64_t> id_to_idx_map_;
+    int digest_ = DAPOL_DIGEST_BLAKE3;                   // create's digest and audit seed (created_: there are some)
+    std::vector<uint8_t> audit_seed_;
+    bool created_ = false;
     std::shared_ptr<Context> ctx_;
     std::shared_ptr<dapol_tree> tree_;
     int height_ = 0;

@@ -230,6 +230,32 @@ int32_t dapol_tree_remove(dapol_tree* tree, size_t k, const uint64_t* leaf_idx);
  * dapol_tree_update.  Larger batches rebuild the tree (an error then leaves the old tree as it was).  dapol_tree_update keeps
  * rebuilding for new leaves whose chains share a node; a caller that only ADDS leaves should call this instead. */
 int32_t dapol_tree_insert(dapol_tree* tree, size_t k, const uint64_t* leaf_idx, const uint64_t* v, const uint8_t* r32);
+/* build_leaf_nodes for k liabilities that JOIN a built tree (ids and values as for dapol_build_leaf_nodes; the height is the tree's):
+ * shuffle_index (src/dapol/mod.rs:408-441) with tree_index_set starting as the tree's current leaf indexes -- candidate c of
+ * liability j is taken when it is a leaf of `tree` now, or held by a liability j' < j of this batch.  Writes nothing to the tree.
+ * Outputs as dapol_build_leaf_nodes: sorted by index (leaf_idx_sorted / v_sorted / r32_sorted / order_sorted, positions within the
+ * batch) and idx_by_entity (may be NULL).  With the tree made from dapol_build_leaf_nodes(L) and nothing removed since, the rows are
+ * those of the new liabilities in dapol_build_leaf_nodes(L ++ new); after removals they are the sequential rule over the leaves that
+ * are left (a freed index can be taken again).  Candidates are looked up in the tree's leaf array on the device: the cost is k hash
+ * chains and k log2(n_leaves) index reads, nothing of the tree's size is allocated, copied or scanned.
+ * Errors, all with the tree untouched: DAPOL_ERR_INVALID_DIGEST_SIZE (digest_id not BLAKE3 / Blake2s), DAPOL_ERR_SPARSITY_TOO_SMALL
+ * (2^height < 2 (n_leaves + k): Dapol::new's rule on the joined count), DAPOL_ERR_DUPLICATED_INTERNAL_ID (an internal id twice IN THE
+ * BATCH), DAPOL_ERR_FAILED_TO_MAP_INDEX (dapol_last_error names the position within the batch), DAPOL_ERR_INVALID_ARGUMENT for a
+ * tree marked invalid and for a shard tree (dapol_tree_build_shard), whose leaf array is not the whole set of taken indexes.
+ * k = 0 does nothing.  The tree holds no ids: an internal id that one of its leaves already carries CANNOT be seen here.  The
+ * caller's id map is the check -- Dapol::insert_liabilities (dapol.hpp) refuses such an id before calling the library. */
+int32_t dapol_tree_derive_leaves(dapol_tree* tree, int32_t digest_id, const uint8_t* audit_seed, size_t audit_seed_len, size_t k,
+                                 const uint8_t* internal_ids, const uint32_t* internal_off, const uint8_t* external_ids,
+                                 const uint32_t* external_off, const uint64_t* values, uint64_t* leaf_idx_sorted, uint64_t* v_sorted,
+                                 uint8_t* r32_sorted, uint32_t* order_sorted, uint64_t* idx_by_entity);
+/* dapol_tree_derive_leaves, then dapol_tree_insert of the result: all or nothing (the derived batch, k x 48 bytes, passes through the
+ * host).  idx_by_entity[k] (may be NULL; written on success only) = where each new liability went.  Afterwards the tree equals
+ * dapol_tree_build over the old and the new leaves, as after dapol_tree_insert.  Refuses what dapol_tree_derive_leaves refuses and
+ * what dapol_tree_insert refuses of a tree (built from a padding tape, workload trees), before anything is written; the same
+ * caveat on ids the tree already carries. */
+int32_t dapol_tree_insert_liabilities(dapol_tree* tree, int32_t digest_id, const uint8_t* audit_seed, size_t audit_seed_len, size_t k,
+                                      const uint8_t* internal_ids, const uint32_t* internal_off, const uint8_t* external_ids,
+                                      const uint32_t* external_off, const uint64_t* values, uint64_t* idx_by_entity);
 /* What the last dapol_tree_update / dapol_tree_insert / dapol_tree_remove on this tree did: 0 = rebuilt, 1 = replaced existing leaves
  * in place, 2 = inserted new leaves in place (disjoint chains), 3 = both, 4 = removed leaves in place, 5 = inserted new leaves in place
  * by dapol_tree_insert's general path (diagnostics; the tree is the same whichever path ran). */
