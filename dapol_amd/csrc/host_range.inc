@@ -169,7 +169,7 @@ static ProveLane carve_lane(const ProvePlan& P, RangeArgs A, uint8_t* base) {
     A.tail_s2 = (sc*)(base + o); o += chunk * T * sizeof(sc);
     A.fs_part = (sc*)(base + o); o += chunk * FS_PARTS_MAX * 3 * sizeof(sc);
     A.stab = P.stab_bytes ? (sc*)(base + o) : nullptr; o += chunk * P.stab_bytes;
-    L.gsacc = (int32_t*)(base + o); o += chunk * P.acc_bytes;
+    L.gsacc = (int32_t*)(base + o); o += chunk * (P.acc_bytes + P.tail_rec_bytes);    // (the tail's window sums share it: ProvePlan::tail_gs)
     o = align_up(o, 256);
     // (the split buffers stay LAST: split_bytes only counts them when a split is in use)
     L.split[0] = (int32_t*)(base + o); o += chunk * (size_t)P.part_split() * 160;
@@ -310,7 +310,9 @@ static int32_t queue_chunk(dapol_ctx* ctx, const ProvePlan& P, const ProveLane& 
     {
         RangeArgs Ai = A;
         Ai.stab = P.stab_tail ? stab_buf : nullptr;           // (k_rp_tail_table also resets the tables for the tail argument)
-        hipLaunchKernelGGL(k_rp_tail_table, dim3(g_tail), dim3(64), 0, st, Ai); LAUNCH_CHECK();
+        if (P.tail_rpl == 4) hipLaunchKernelGGL(k_rp_tail_table4, dim3(nblk(cb * (size_t)(2 * P.tail_n / 4), 64)), dim3(64), 0, st, Ai);
+        else hipLaunchKernelGGL(k_rp_tail_table, dim3(g_tail), dim3(64), 0, st, Ai);
+        LAUNCH_CHECK();
     }
     // The remaining rounds: the same never-fold kernels on the length-T argument over the proof's own table.
     RangeArgs At = A;
@@ -322,7 +324,11 @@ static int32_t queue_chunk(dapol_ctx* ctx, const ProvePlan& P, const ProveLane& 
     for (int k = 0; k < P.tail_lgn; k++) {
         hipLaunchKernelGGL(k_rp_round_prep, dim3(g_tail), dim3(64), 0, st, At, k); LAUNCH_CHECK();
         hipLaunchKernelGGL(k_rp_round_ip, dim3(g_wave), dim3(64), 0, st, At, k); LAUNCH_CHECK();
-        launch_msm_tail(st, At, tvt, k, P.tail_lpl); LAUNCH_CHECK();
+        if (P.tail_gs) {                                      // a lane per (proof, list, window), then Horner per list
+            hipLaunchKernelGGL(k_rp_tail_gs, dim3(nblk(2 * cb, TAIL_GS_LISTS)), dim3(TAIL_GS_BLOCK), 0, st, At, tvt, k, L.gsacc); LAUNCH_CHECK();
+            hipLaunchKernelGGL(k_rp_tail_combine, dim3(nblk(2 * cb, 64)), dim3(64), 0, st, At, L.gsacc);
+        } else launch_msm_tail(st, At, tvt, k, P.tail_lpl);
+        LAUNCH_CHECK();
         LAUNCH_FS(k_rp_round_finish, fs_shape, cb, st, At, ctx->tv, k); LAUNCH_CHECK();
         hipLaunchKernelGGL(k_rp_fold, dim3(fold_blocks(At, cb, k)), dim3(256), 0, st, At, k);
         LAUNCH_CHECK();

@@ -342,7 +342,7 @@ __global__ __launch_bounds__(64) void k_rp_A_lane(RangeArgs A, TableView tbl) {
 // meet in a shuffle reduction (wave_reduce_point: no LDS, no barrier).  This is the form of calls of fewer than 8,192 proofs -- mid-size
 // and small calls --, of the tail argument over a proof's own tables and of the verifier's generator MSM; calls of at least 8,192 proofs run
 // the plain rounds and the materialisation generator-stationary instead (kernels_range_gs.h), which reads the same table rows
-// out of the Infinity Cache.
+// out of the Infinity Cache, and in full chunks the tail rounds with a lane per window as well (k_rp_tail_gs, same file).
 #ifndef DAPOL_MSM_OCC
 #define DAPOL_MSM_OCC 3          // resident wavefronts per SIMD the register allocation is bounded for
 #endif
@@ -588,13 +588,10 @@ __device__ __forceinline__ void build_niels_row(int32_t* row) {
     niels_store_entry(row, id);
 }
 
-// One lane per materialised generator: its table row, and the tail argument's vectors: a, b = the first T entries of the
-// folded vectors, coefficients s = 1.
-__global__ __launch_bounds__(64) void k_rp_tail_table(RangeArgs A) {
-    const int T = A.tail_n, bpp = (2 * T) >> 6;                  // blocks per proof
-    size_t b = blockIdx.x / bpp;
-    int g = (int)(blockIdx.x % bpp) * 64 + threadIdx.x;          // row: G'_g (g < T) or H'_(g-T)
-    build_niels_row<TAIL_ENTRIES>(A.tailT + (b * (size_t)(2 * T) + g) * TAIL_ROW_WORDS);
+// The tail argument's vectors of row g (G'_g for g < T, else H'_(g-T)) of proof b: a, b = the first T entries of the folded
+// vectors, coefficients s = 1.
+__device__ __forceinline__ void tail_row_vectors(const RangeArgs& A, size_t b, int g) {
+    const int T = A.tail_n;
     sc one, v;
     sc_zero(one); one.v[0] = 1;                              // plain 1 (the s-vectors are kept in plain form)
     int i = g < T ? g : g - T;
@@ -602,6 +599,94 @@ __global__ __launch_bounds__(64) void k_rp_tail_table(RangeArgs A) {
     st_sc((g < T ? A.tail_s1 : A.tail_s2) + b * T + i, one);
     ld_sc(v, (g < T ? A.a : A.b) + b * A.N + i);
     st_sc((g < T ? A.tail_a : A.tail_b) + b * T + i, v);
+}
+// One lane per materialised generator: its table row, and the tail argument's vectors.
+__global__ __launch_bounds__(64) void k_rp_tail_table(RangeArgs A) {
+    const int T = A.tail_n, bpp = (2 * T) >> 6;                  // blocks per proof
+    size_t b = blockIdx.x / bpp;
+    int g = (int)(blockIdx.x % bpp) * 64 + threadIdx.x;          // row: G'_g (g < T) or H'_(g-T)
+    build_niels_row<TAIL_ENTRIES>(A.tailT + (b * (size_t)(2 * T) + g) * TAIL_ROW_WORDS);
+    tail_row_vectors(A, b, g);
+}
+
+// The same rows with ONE field inversion per four of them (ProvePlan::tail_rpl = 4): build_niels_row spends about 265 of its 510
+// field products on the inversion of the row's Z product, and lanes of a SIMD cannot share one -- a lane can, over rows of its own.
+// A lane owns the rows g0 + k (2T / 4), k = 0..3 (adjacent lanes, adjacent rows, as above).  Pass 1, per row: the multiples, X | Y | Z
+// kept in their slots, and the product of the row's Z's.  One inversion of the product of the four row products gives each row's
+// inverse back (nine products).  Pass 2, per row: the prefix products again from the stored Z's, then build_niels_row's backward
+// loop.  The affine coordinates are the same field elements as above.  ONE copy of each pass (instruction cache): the rows are
+// trips of a loop, the row's product / inverse picked by selects.
+template <int ENTRIES>
+__device__ __forceinline__ void niels_row_multiples(int32_t* row, fe& total) {
+    ge_p3 base, mul;
+    ld_p3(base, row);
+    mul = base;
+#pragma nounroll
+    for (int e = 1; e < ENTRIES; e++) {
+        if (e > 1) { ge_p3 t; ge_add(t, mul, base); mul = t; }
+        int32_t* slot = row + e * 32;
+        for (int i = 0; i < FE_NL; i++) { slot[i] = mul.X.v[i]; slot[FE_NL + i] = mul.Y.v[i]; slot[2 * FE_NL + i] = mul.Z.v[i]; }
+        if (e == 1) total = mul.Z;
+        else { fe t; fe_mul(t, total, mul.Z); total = t; }
+    }
+}
+template <int ENTRIES>
+__device__ __forceinline__ void niels_row_finish(int32_t* row, fe inv) {          // inv = 1 / (the product of the row's Z's)
+    fe pre[ENTRIES - 1];
+#pragma unroll
+    for (int e = 1; e < ENTRIES; e++) {
+        const int32_t* slot = row + e * 32;
+        fe Z;
+        for (int i = 0; i < FE_NL; i++) Z.v[i] = slot[2 * FE_NL + i];
+        if (e == 1) pre[0] = Z;
+        else fe_mul(pre[e - 1], pre[e - 2], Z);
+    }
+#pragma unroll
+    for (int e = ENTRIES - 1; e >= 1; e--) {
+        int32_t* slot = row + e * 32;
+        fe X, Y, Z, zi, x, y;
+        for (int i = 0; i < FE_NL; i++) { X.v[i] = slot[i]; Y.v[i] = slot[FE_NL + i]; Z.v[i] = slot[2 * FE_NL + i]; }
+        if (e > 1) { fe_mul(zi, inv, pre[e - 2]); fe t; fe_mul(t, inv, Z); inv = t; }
+        else zi = inv;
+        fe_mul(x, X, zi);
+        fe_mul(y, Y, zi);
+        ge_niels q;
+        ge_to_niels(q, x, y);
+        niels_store_entry(slot, q);
+    }
+    ge_niels id;
+    ge_niels_identity(id);
+    niels_store_entry(row, id);
+}
+// grid = ceil(cb * (2T / 4) / 64) blocks of 64 (2T is a multiple of 4 for every tail length)
+__global__ __launch_bounds__(64) void k_rp_tail_table4(RangeArgs A) {
+    const int T = A.tail_n, LP = (2 * T) >> 2;                   // lanes per proof
+    const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const size_t b = t / (size_t)LP;
+    if (b >= A.B) return;
+    const int g0 = (int)(t - b * (size_t)LP);
+    int32_t* rows = A.tailT + b * (size_t)(2 * T) * TAIL_ROW_WORDS;
+    fe t0, t1, t2, t3;
+#pragma nounroll
+    for (int k = 0; k < 4; k++) {
+        fe tot;
+        niels_row_multiples<TAIL_ENTRIES>(rows + (size_t)(g0 + k * LP) * TAIL_ROW_WORDS, tot);
+        if (k == 0) t0 = tot; else if (k == 1) t1 = tot; else if (k == 2) t2 = tot; else t3 = tot;
+    }
+    fe p01, p23, all, inv, i01, i23;
+    fe_mul(p01, t0, t1);
+    fe_mul(p23, t2, t3);
+    fe_mul(all, p01, p23);
+    fe_invert(inv, all);
+    fe_mul(i01, inv, p23);                                       // 1 / (t0 t1)
+    fe_mul(i23, inv, p01);                                       // 1 / (t2 t3)
+#pragma nounroll
+    for (int k = 0; k < 4; k++) {
+        fe ri;
+        fe_mul(ri, k < 2 ? i01 : i23, k == 0 ? t1 : (k == 1 ? t0 : (k == 2 ? t3 : t2)));
+        niels_row_finish<TAIL_ENTRIES>(rows + (size_t)(g0 + k * LP) * TAIL_ROW_WORDS, ri);
+        tail_row_vectors(A, b, g0 + k * LP);
+    }
 }
 
 // Digits of the s-vectors themselves, in the S layout (list 0 = s_G over G, list 1 = s_H over H): input of the

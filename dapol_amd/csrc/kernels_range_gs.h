@@ -353,4 +353,61 @@ __global__ __launch_bounds__(64) void k_rp_mat_gs_horner(RangeArgs A, int side, 
     st_p3(A.tailT + (p * (size_t)(2 * T) + (size_t)(side * T + cls0 + c)) * TAIL_ROW_WORDS, acc);
 }
 
+// ------------------------------------------------------------------------------------------------ the tail rounds
+// Round `round` of the tail argument (k_rp_msm<MSM_TAIL, .>: the proof's own table, T terms a list, TAIL_NWIN windows of TAIL_WBITS
+// bits) with a lane per ACCUMULATOR: (proof, list, window), the windows of a list on adjacent lanes.  The TAIL_NWIN lanes of a list
+// walk its T rows in the same order, so a lookup instruction reads entries of ONE 2,176-byte row per list it covers (at most 17
+// lines) where the proof-stationary kernel's 64 lanes read 64 lines of 16 proofs' tables; no doubling in the loop, the window sums
+// of a list are combined afterwards (k_rp_tail_combine).  Same terms, same term -> generator map and the same digit matrix as the
+// proof-stationary kernel (k_rp_round_prep writes it: proof-major, window-major, TP = 2T), four terms per 16-byte digit load.
+// TAIL_NWIN = 51 does not divide a wavefront: TAIL_GS_LISTS whole lists per block of 256 threads (255 lanes at 51 windows); the
+// lanes left over, and those of lists past the last proof's, do nothing.
+// recs: one 36-word record (X | Y | Z | T, st_p3's order) per lane, record (2 p + side) * TAIL_NWIN + w -- adjacent lanes write
+// adjacent records, and k_rp_tail_combine's lane reads one list's records in a row.
+enum { TAIL_GS_BLOCK = 256, TAIL_GS_LISTS = TAIL_GS_BLOCK / TAIL_NWIN, TAIL_REC_WORDS = 4 * FE_NL };
+static_assert(TAIL_GS_LISTS >= 1, "a list's windows fit a block");
+__global__ __launch_bounds__(TAIL_GS_BLOCK, DAPOL_GS_OCC) void k_rp_tail_gs(RangeArgs A, TableView tbl, int round, int32_t* __restrict__ recs) {
+    const int li = (int)threadIdx.x / TAIL_NWIN, w = (int)threadIdx.x - li * TAIL_NWIN;
+    const size_t list = (size_t)blockIdx.x * TAIL_GS_LISTS + li;               // 2 p + side
+    if (li >= TAIL_GS_LISTS || list >= 2 * A.B) return;
+    const size_t p = list >> 1;
+    const int side = (int)(list & 1);
+    tbl.base += p * (size_t)(2 * A.N) * tbl.row_words();
+    // (term q of list `side` at 64 (q / 32) + q % 32 + 32 side of a window's digit row: runs of four are 16 bytes, aligned)
+    const dig_t* dw = A.dig + (p * A.nwin + (size_t)w) * (size_t)A.TP + 32 * side;
+    ge_p3 acc;
+    ge_identity(acc);
+    dapol_v4i d4 = *reinterpret_cast<const dapol_v4i*>(dw), dn = d4;          // (digits one quad ahead, as in k_rp_msm_gs)
+#pragma nounroll
+    for (int q = 0; q < A.N; q++) {
+        if ((q & 3) == 0 && q + 4 < A.N) dn = *reinterpret_cast<const dapol_v4i*>(dw + 64 * ((q + 4) >> 5) + ((q + 4) & 31));
+        const int d = d4.x;
+        d4.x = d4.y; d4.y = d4.z; d4.z = d4.w;
+        if ((q & 3) == 3) d4 = dn;
+        bool isH;
+        const int j = term_generator(round, A.N, A.lgN, side, q, isH);          // (uniform over a list)
+        tbl_madd(acc, tbl, j + (isH ? A.N : 0), d);
+    }
+    st_p3(recs + (list * TAIL_NWIN + (size_t)w) * TAIL_REC_WORDS, acc);
+}
+
+// P_side[p] = sum_w 2^(TAIL_WBITS w) * (window sum w of the list): Horner from the top window over the list's records, one lane
+// per (proof, list); the point goes where k_rp_msm<MSM_TAIL, .> leaves it (k_rp_round_finish reads P0 / P1).
+__global__ __launch_bounds__(64) void k_rp_tail_combine(RangeArgs A, const int32_t* __restrict__ recs) {
+    const size_t list = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (list >= 2 * A.B) return;
+    const int32_t* rp = recs + list * TAIL_NWIN * TAIL_REC_WORDS;
+    ge_p3 acc, t2, r;
+    ld_p3(acc, rp + (size_t)(A.nwin - 1) * TAIL_REC_WORDS);
+#pragma nounroll
+    for (int w = A.nwin - 2; w >= 0; w--) {
+#pragma nounroll
+        for (int d = 0; d < A.wbits; d++) ge_dbl(acc, acc, d == A.wbits - 1);
+        ld_p3(t2, rp + (size_t)w * TAIL_REC_WORDS);
+        ge_add(r, acc, t2);
+        acc = r;
+    }
+    st_p3(((list & 1) ? A.P1 : A.P0) + (list >> 1) * 40, acc);
+}
+
 }  // namespace dapol

@@ -1,6 +1,6 @@
 // What one call of the batched range prover chooses, as pure host arithmetic over (n, m, B), the options, the table geometry and the
 // scratch budget: tail length, small-call / generator-stationary / proof-stationary regime, Fiat-Shamir shape, chunk size and chunks
-// in flight, lanes per list, the MSM / materialisation / quad splits, slices and tile rows.  No HIP call and no dapol_ctx: the launcher
+// in flight, lanes per list, the order of the tail rounds, the MSM / materialisation / quad splits, slices and tile rows.  No HIP call and no dapol_ctx: the launcher
 // (host_range.inc: range_prove_device) fills a ProveShape from its context, and tests/cpp/prove_plan_host.cpp replays recorded
 // shapes against tests/golden/prove_plan.json on the CPU.  The includer provides knob() and the layout constants of the kernel
 // headers (sc, dig_t, ProofState, FE_NL, TAIL_*, STAB_*, MAT_GROUP, GS_*).
@@ -10,6 +10,8 @@
 #include <cstdlib>
 
 enum { FS_PARTS_MAX = 8 };        // most wavefronts per proof of k_rp_poly / k_rp_lr in small calls
+enum { TAIL_RPL_DEFAULT = 4 };    // the plan's own choice of ProvePlan::tail_rpl for full chunks (1 or 4)
+enum { TAIL_GS_DEFAULT = 1 };     // the plan's own choice of ProvePlan::tail_gs for full chunks (0: only DAPOL_TAIL_ORDER=gs turns it on)
 
 struct ProveShape {
     int n, m;
@@ -40,6 +42,15 @@ struct ProvePlan {
     bool big_batch;
     int lpl, tail_lpl;                // set by finalise()
     bool side_A;
+    // The tail rounds a lane per (proof, list, window) instead of proof-stationary (kernels_range_gs.h: k_rp_tail_gs); set by finalise().
+    // Its window sums live in the chunk's sweep accumulators, which are idle during the tail: tail_rec_bytes per proof on top of
+    // acc_bytes only where the order is FORCED onto a call whose accumulators are absent or smaller (tail_order).
+    bool tail_gs;
+    int tail_order;                   // DAPOL_TAIL_ORDER: -1 = ps, +1 = gs (forced for any call with a tail), 0 = the plan's choice
+    size_t tail_rec_bytes;
+    // Rows of the proof's tail table a lane of k_rp_tail_table builds: 1, or 4 with one field inversion between them
+    // (k_rp_tail_table4); set by finalise().  tail_rpl_forced: DAPOL_TAIL_ROWS_PER_LANE = 1 / 4 (0: the plan's choice).
+    int tail_rpl, tail_rpl_forced;
     // what the per-chunk choices below start from
     int gs_tile, gs_slices_forced, mat_cpl_forced;
     bool gs_tile_set, a_lane_ok;
@@ -144,6 +155,9 @@ static int msm_lanes_per_list(int N, bool big_batch = false, const char* e = kno
     return N >= 1024 ? (big_batch ? 2 : 8) : (N >= 256 ? 16 : 32);
 }
 
+// Bytes per proof of the window sums of one tail round in the lane-per-accumulator order: two lists x TAIL_NWIN records of X | Y | Z | T.
+static size_t tail_rec_need() { return (size_t)2 * TAIL_NWIN * 4 * FE_NL * 4; }
+
 static ProvePlan plan_range_prove(const ProveShape& s) {
     ProvePlan P{};
     const size_t B = s.B;
@@ -246,8 +260,13 @@ static ProvePlan plan_range_prove(const ProveShape& s) {
     P.acc_slots = acc_slots;
     P.acc_bytes = gs_possible ? (size_t)acc_slots * s.nwin * 4 * FE_NL * 4 : 0;
     P.stab_bytes = (P.stab_main || P.stab_tail) ? (size_t)2 * 2 * STAB_N * sizeof(sc) : 0;     // coefficient tables (two buffers x two sides)
+    // DAPOL_TAIL_ORDER = ps / gs forces the order of the tail rounds (ProvePlan::tail_gs) for any call that has a tail.  A forced gs
+    // needs 2 x TAIL_NWIN records per proof whatever the regime; the plan's own choice only ever uses accumulators that are there.
+    if (const char* e = knob("DAPOL_TAIL_ORDER")) P.tail_order = (e[0] == 'g' && e[1] == 's' && !e[2]) ? 1 : ((e[0] == 'p' && e[1] == 's' && !e[2]) ? -1 : 0);
+    if (const char* e = knob("DAPOL_TAIL_ROWS_PER_LANE")) { int v = atoi(e); if (v == 1 || v == 4) P.tail_rpl_forced = v; }
+    P.tail_rec_bytes = (P.tail_order > 0 && tail_n && P.acc_bytes < tail_rec_need()) ? tail_rec_need() - P.acc_bytes : 0;
     P.per_proof = 4 * (size_t)N * sizeof(sc) + dig_elems * sizeof(dig_t) + (sizeof(ProofState) + 15) / 16 * 16 + 3 * 160 +
-                  2 * T * TAIL_ROW_WORDS * 4 + 4 * T * sizeof(sc) + FS_PARTS_MAX * 3 * sizeof(sc) + P.stab_bytes + P.acc_bytes;
+                  2 * T * TAIL_ROW_WORDS * 4 + 4 * T * sizeof(sc) + FS_PARTS_MAX * 3 * sizeof(sc) + P.stab_bytes + P.acc_bytes + P.tail_rec_bytes;
     // ONE chunk in flight by default since round 4 (dapol_options::streams / DAPOL_STREAMS = 2..4 puts more in flight, on the
     // context's side streams with their own shares of the scratch).  History: round 1 measured +4.8 % for two chunks in flight
     // (the scalar-vector kernels and the Fiat-Shamir chains of one chunk under the other's MSM, profiles/archive/r01_streams_ab.txt);
@@ -356,6 +375,18 @@ void ProvePlan::finalise(const ProveShape& s, size_t chunk_, int nlanes_) {
         const int cand[4] = {2, 4, 8, 32};
         tail_lpl = pick_lanes_per_list(chunk, tail_n, TAIL_NWIN, TAIL_WBITS, cand, 4, s.resident_waves, (size_t)s.n_cu * 4, true);
     }
+    // The tail rounds with a lane per (proof, list, window): swept calls of at least 1,024 generators a side whose chunk is a full one
+    // (65,536 proofs or more: 6.7 M lanes, the chip 34 times over) -- the shape it was measured at: a round of a 131,072-proof chunk
+    // 26.3 + 2.3 ms against 34.9 proof-stationary, the headline +1.06 / +1.48 % in two interleaved pairs against 0.15 % between the
+    // parent's own runs (profiles/tail_order_ab.txt).  Smaller chunks have the chip to themselves and keep the proof-stationary
+    // kernel with the lanes per list picked above (not measured in the new order).  Only where the sweep's accumulators hold a
+    // round's records (15 windows of 17 bits: 69,120 B a proof against 14,688).
+    tail_gs = tail_n != 0 && (tail_order > 0 || (tail_order == 0 && TAIL_GS_DEFAULT && gs && !small_call && N >= 1024 && chunk >= 65536 && acc_bytes >= tail_rec_need()));
+    // Four table rows a lane (a quarter of the inversions, four times the chain of a lane): full chunks as above, where the launch is
+    // tens of wavefront rounds long whichever way (the headline +0.20 / +0.51 % against one row a lane in two interleaved rounds, the
+    // parent's own runs 0.26 % apart: same file); never where a proof's 2T rows do not divide by four.
+    tail_rpl = tail_rpl_forced ? tail_rpl_forced : ((TAIL_RPL_DEFAULT == 4 && gs && !small_call && N >= 1024 && chunk >= 65536) ? 4 : 1);
+    if (!tail_n || (2 * tail_n) % 4 != 0) tail_rpl = 1;
     // a small call's A commitment (a chain of additions on one wavefront) runs beside the S commitment's MSM
     side_A = small_call && nlanes == 1 && s.B <= 64 && !s.timed && !knob("DAPOL_NO_SIDE_A");
 }
