@@ -48,6 +48,12 @@ static int32_t fail(int32_t code, const char* msg) {
         if (e_ != hipSuccess) return fail_hip(e_, #x, __FILE__, __LINE__); \
     } while (0)
 #define LAUNCH_CHECK() HIPCHK(hipGetLastError())
+// A step that reports with a DAPOL_* code of its own: anything but DAPOL_OK ends the caller with it.
+#define RCCHK(x)                   \
+    do {                           \
+        int32_t rc_ = (x);         \
+        if (rc_) return rc_;       \
+    } while (0)
 
 // The DAPOL_* environment variables are measurement knobs (A/B switches of tools/ and tests/).  They are read only when the
 // process has opted in -- DAPOL_ENV_KNOBS set to anything but "0", or dapol_env_knobs(1) -- so that a host embedding the library
@@ -317,7 +323,7 @@ int32_t dapol_ctx_create_opts(int32_t device, int32_t max_parties, int32_t diges
         else (void)hipGetLastError();
     }
     struct Guard { dapol_ctx* c; ~Guard() { if (c) dapol_ctx_destroy(c); } } guard{c};
-    { int32_t rc_ = ctx_make_streams(c); if (rc_) return rc_; }
+    RCCHK(ctx_make_streams(c));
     const int P = max_parties;
     // window width: the widest (<= 17 bits: wider measured slower, profiles/r01_wbits_ab4.txt) whose tables fit the budget --
     // DAPOL_TABLE_GB if set, else 40 GB but never more than 30 % of the memory that is free right now (a second context on

@@ -266,7 +266,7 @@ static int32_t tree_build_device(dapol_ctx* ctx, int index_bits, int shard_bits,
         bound[k + 1] = bound[k];
         if (bits_above < 40 && ((size_t)1 << bits_above) < bound[k + 1]) bound[k + 1] = (size_t)1 << bits_above;
     }
-    { int32_t rc_ = carve_arena(t, bound, st); if (rc_) return rc_; }
+    RCCHK(carve_arena(t, bound, st));
     const uint32_t n32 = (uint32_t)n;
     HIPCHK(hipMemcpyAsync(cnt.p, &n32, 4, hipMemcpyHostToDevice, st));
     const bool phased = n <= (size_t)TREE_SMALL_MAX && height >= 1 && !knob("DAPOL_TREE_LEVELWISE") && !d_tape;     // (tape mode: the level-wise kernel reads the tape)

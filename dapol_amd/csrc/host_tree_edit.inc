@@ -55,11 +55,11 @@ static int32_t tree_update_incremental(dapol_tree_owned* own, const HostLeaves& 
     HIPCHK(sc.ensure(own));
     uint8_t* d = own->upd_scratch.p;
     std::vector<uint8_t> stage;
-    { int32_t rc_ = upload_edits(own, E, stage); if (rc_) return rc_; }
+    RCCHK(upload_edits(own, E, stage));
     HIPCHK(hipMemsetAsync(d + o_miss, 0, 8, st));
     TreeUpdArgs U{k, H, (const uint64_t*)(d + o_idx), (const uint64_t*)(d + o_v), (const uint32_t*)(d + o_r), (uint32_t*)(d + o_pos), (int32_t*)(d + o_dP),
                   (uint64_t*)(d + o_dv), (uint32_t*)(d + o_dr), (uint32_t*)(d + o_miss), d + o_found, nullptr};
-    hipLaunchKernelGGL(k_tree_upd_find, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, U);
+    hipLaunchKernelGGL(k_tree_find_paths, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, TreeFind{k, H, U.idx, U.pos, nullptr, U.missing, U.found});
     LAUNCH_CHECK();
     uint32_t missing = 0;
     HIPCHK(hipMemcpyAsync(&missing, d + o_miss, 4, hipMemcpyDeviceToHost, st));
@@ -70,7 +70,7 @@ static int32_t tree_update_incremental(dapol_tree_owned* own, const HostLeaves& 
     if (test_knob("DAPOL_TEST_FAIL_UPDATE_MIDWAY")) return fail(DAPOL_ERR_HIP, "injected failure between the leaf update and the re-merge (test knob)");
     hipLaunchKernelGGL(k_tree_upd_leaves, dim3(nblk(k, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, U);
     LAUNCH_CHECK();
-    if (H >= 1) { int32_t rc_ = rehash_paths(own, U); if (rc_) return rc_; }
+    if (H >= 1) RCCHK(rehash_paths(own, U));
     HIPCHK(hipStreamSynchronize(st));
     poison.armed = false;
     *done = true;
@@ -148,11 +148,38 @@ static int32_t adopt_levels(dapol_tree_owned* own, const StagedLevels& S, std::v
     return DAPOL_OK;
 }
 
-// What k_tree_ins_plan_all returned for a batch (dapol_tree_insert plans once, whichever insert path then runs).
+// The tree's node counts from its level sizes: every parent has two children, and those that are not real are padding nodes.
+static void recount_nodes(dapol_tree_owned* own) {
+    own->n_real = 0;
+    own->n_pad = 0;
+    for (int t = 0; t <= own->height; t++) {
+        own->n_real += own->levels[t].n;
+        if (t < own->height) own->n_pad += 2 * (uint64_t)own->levels[t + 1].n - own->levels[t].n;
+    }
+}
+
+// What k_tree_ins_plan returned for a batch (dapol_tree_insert plans once, whichever insert path then runs).
 struct InsPlanRead {
     std::vector<uint32_t> m, pos;        // [k], [k][H + 1]
     uint32_t flag = 0;                   // bit 1: two chains share a new node; bit 2: an index is a leaf already
 };
+// I1 / J1: plans the k sorted indexes at d_idx into d_m | d_pos | d_flag (cleared by the caller) and reads the rows back.  all_levels:
+// the search goes on to the root (J1) instead of ending at a leaf's first existing ancestor.  Nothing of the tree is written.
+static int32_t run_insert_plan(dapol_tree_owned* own, size_t k, const uint64_t* d_idx, uint32_t* d_m, uint32_t* d_pos, uint32_t* d_flag, bool all_levels,
+                               InsPlanRead& R) {
+    hipStream_t st = own->ctx->stream;
+    const size_t S1 = (size_t)own->height + 1;
+    const TreeInsPlan P{k, own->height, d_idx, d_m, d_pos, d_flag};
+    if (all_levels) hipLaunchKernelGGL(k_tree_ins_plan<false>, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, P);
+    else hipLaunchKernelGGL(k_tree_ins_plan<true>, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, P);
+    LAUNCH_CHECK();
+    R.m.resize(k); R.pos.resize(k * S1);
+    HIPCHK(hipMemcpyAsync(R.m.data(), d_m, k * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(R.pos.data(), d_pos, k * S1 * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&R.flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return DAPOL_OK;
+}
 // The incremental path for NEW leaves (kernels_ctx_tree.h, "incremental insert"): E sorted, distinct, none of them in the tree.
 // *done = false and nothing written when two new chains share a node (the caller rebuilds).  pre: the batch has been planned already
 // (no chains shared, every index new); its rows hold what I1 would write.
@@ -170,24 +197,17 @@ static int32_t tree_insert_incremental(dapol_tree_owned* own, const HostLeaves& 
     HIPCHK(sc.ensure(own));
     uint8_t* d = own->upd_scratch.p;
     std::vector<uint8_t> stage;
-    { int32_t rc_ = upload_edits(own, E, stage); if (rc_) return rc_; }
+    RCCHK(upload_edits(own, E, stage));
     HIPCHK(hipMemcpyAsync(d + o_seed, own->pad_seed, 32, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d + o_flag, 0, 8, st));
-    std::vector<uint32_t> hm_own, hins_own;
+    InsPlanRead planned;
     if (pre) HIPCHK(hipMemcpyAsync(d + o_m, pre->m.data(), k * 4, hipMemcpyHostToDevice, st));
     else {
-        TreeInsPlan P{k, H, (const uint64_t*)(d + o_idx), (uint32_t*)(d + o_m), (uint32_t*)(d + o_ins), (uint32_t*)(d + o_flag)};
-        hipLaunchKernelGGL(k_tree_ins_plan, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, P);
-        LAUNCH_CHECK();
-        hm_own.resize(k); hins_own.resize(k * S1);
-        uint32_t conflict = 0;
-        HIPCHK(hipMemcpyAsync(hm_own.data(), d + o_m, k * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(hins_own.data(), d + o_ins, k * S1 * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&conflict, d + o_flag, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (conflict) return DAPOL_OK;                      // chains that share a node (or an index that exists): the rebuild handles it
+        RCCHK(run_insert_plan(own, k, (const uint64_t*)(d + o_idx), (uint32_t*)(d + o_m), (uint32_t*)(d + o_ins), (uint32_t*)(d + o_flag), false, planned));
+        if (planned.flag) return DAPOL_OK;                  // chains that share a node (or an index that exists): the rebuild handles it
+        pre = &planned;
     }
-    const std::vector<uint32_t>&hm = pre ? pre->m : hm_own, &hins = pre ? pre->pos : hins_own;
+    const std::vector<uint32_t>&hm = pre->m, &hins = pre->pos;
     const InsertPlan plan = plan_insert(k, H, hm.data(), hins.data());
     HIPCHK(hipMemcpyAsync(d + o_new, plan.newpos.data(), k * S1 * 4, hipMemcpyHostToDevice, st));
     if (!plan.lvl_flat.empty()) HIPCHK(hipMemcpyAsync(d + o_lvl, plan.lvl_flat.data(), plan.lvl_flat.size() * 4, hipMemcpyHostToDevice, st));
@@ -196,10 +216,10 @@ static int32_t tree_insert_incremental(dapol_tree_owned* own, const HostLeaves& 
     std::vector<RelayoutDel> gains((size_t)plan.max_m);
     for (int t = 0; t < plan.max_m; t++) gains[t] = RelayoutDel{d_lvl + plan.lvl_off[t], plan.gained(t), d_lvl + plan.lvl_off[t + 1], plan.gained(t + 1)};
     StagedLevels staged;
-    { int32_t rc_ = relayout_levels(own, gains, false, staged); if (rc_) return rc_; }
+    RCCHK(relayout_levels(own, gains, false, staged));
     TreePoison poison{own, true};                            // the tree's own state changes from here on
     std::vector<LevelView> hv;
-    { int32_t rc_ = adopt_levels(own, staged, hv); if (rc_) return rc_; }
+    RCCHK(adopt_levels(own, staged, hv));
     TreeInsArgs I{k, H, (const uint64_t*)(d + o_idx), (const uint64_t*)(d + o_v), (const uint32_t*)(d + o_r), (const uint32_t*)(d + o_m),
                   (const uint32_t*)(d + o_new), (uint32_t*)(d + o_pos), (int32_t*)(d + o_dP), (uint64_t*)(d + o_dv), (uint32_t*)(d + o_dr),
                   (const uint32_t*)(d + o_seed)};
@@ -207,7 +227,7 @@ static int32_t tree_insert_incremental(dapol_tree_owned* own, const HostLeaves& 
     LAUNCH_CHECK();
     TreeUpdArgs U{k, H, (const uint64_t*)(d + o_idx), (const uint64_t*)(d + o_v), (const uint32_t*)(d + o_r), (uint32_t*)(d + o_pos), (int32_t*)(d + o_dP),
                   (uint64_t*)(d + o_dv), (uint32_t*)(d + o_dr), (uint32_t*)(d + o_flag), nullptr, (const uint32_t*)(d + o_m)};
-    { int32_t rc_ = rehash_paths(own, U); if (rc_) return rc_; }
+    RCCHK(rehash_paths(own, U));
     HIPCHK(hipStreamSynchronize(st));
     for (size_t j = 0; j < k; j++) { own->n_real += hm[j]; own->n_pad += (uint64_t)hm[j] - 2; }     // m - 1 new padding nodes, one dropped
     poison.armed = false;
@@ -227,15 +247,7 @@ static int32_t insert_plan_all(dapol_tree_owned* own, const HostLeaves& E, InsPl
     uint8_t* d = own->upd_scratch.p;
     HIPCHK(hipMemcpyAsync(d, E.idx.data(), k * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d + o_flag, 0, 8, st));
-    TreeInsPlan P{k, own->height, (const uint64_t*)d, (uint32_t*)(d + o_m), (uint32_t*)(d + o_pos), (uint32_t*)(d + o_flag)};
-    hipLaunchKernelGGL(k_tree_ins_plan_all, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, P);
-    LAUNCH_CHECK();
-    R.m.resize(k); R.pos.resize(k * S1);
-    HIPCHK(hipMemcpyAsync(R.m.data(), d + o_m, k * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(R.pos.data(), d + o_pos, k * S1 * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&R.flag, d + o_flag, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return DAPOL_OK;
+    return run_insert_plan(own, k, (const uint64_t*)d, (uint32_t*)(d + o_m), (uint32_t*)(d + o_pos), (uint32_t*)(d + o_flag), true, R);
 }
 // The general in-place path of dapol_tree_insert: E sorted, distinct, all new and in range, R = its plan rows; chains may share
 // nodes.
@@ -254,44 +266,40 @@ static int32_t tree_insert_general(dapol_tree_owned* own, const HostLeaves& E, c
     HIPCHK(sc.ensure(own));
     uint8_t* d = own->upd_scratch.p;
     std::vector<uint8_t> stage;
-    { int32_t rc_ = upload_edits(own, E, stage); if (rc_) return rc_; }
+    RCCHK(upload_edits(own, E, stage));
     HIPCHK(hipMemcpyAsync(d + o_flat, plan.flat.data(), plan.flat.size() * 4, hipMemcpyHostToDevice, st));
     const uint32_t* dw = (const uint32_t*)(d + o_flat);
     std::vector<RelayoutDel> gains((size_t)plan.D);
     for (int t = 0; t < plan.D; t++)
         gains[t] = RelayoutDel{dw + plan.gain_off[t], (uint32_t)plan.gain[t].size(), dw + plan.gain_off[t + 1], (uint32_t)plan.gain[t + 1].size()};
     StagedLevels staged;
-    { int32_t rc_ = relayout_levels(own, gains, false, staged); if (rc_) return rc_; }
+    RCCHK(relayout_levels(own, gains, false, staged));
     TreePoison poison{own, true};                            // the tree's own state changes from here on
     std::vector<LevelView> hv;
-    { int32_t rc_ = adopt_levels(own, staged, hv); if (rc_) return rc_; }
+    RCCHK(adopt_levels(own, staged, hv));
     if (test_knob("DAPOL_TEST_FAIL_INSERT_MIDWAY")) return fail(DAPOL_ERR_HIP, "injected failure between the relayout and the new nodes (test knob)");
     int32_t* node_ext = (int32_t*)(d + o_node);
-    TreeInsGeneral G{n_new, k, n_pad, dw + plan.lvl_off, dw + plan.pos_off, dw + plan.parent_off, dw + plan.sib_off, dw + plan.idx_lo_off, dw + plan.idx_hi_off,
-                     dw + plan.leaf_off, dw + plan.pad_lvl_off, dw + plan.pad_pos_off, (const uint64_t*)(d + k * 8), (const uint32_t*)(d + k * 16), dw,
-                     node_ext, (int32_t*)(d + o_pad), (uint32_t)slots};
+    int32_t* pad_ext = (int32_t*)(d + o_pad);
+    TreeInsGeneral G{n_new, k, dw + plan.lvl_off, dw + plan.pos_off, dw + plan.parent_off, dw + plan.sib_off, dw + plan.idx_lo_off, dw + plan.idx_hi_off,
+                     dw + plan.leaf_off, (const uint64_t*)(d + k * 8), (const uint32_t*)(d + k * 16), node_ext};
     hipLaunchKernelGGL(k_tree_ins_struct, dim3(nblk(n_new, 64)), dim3(64), 0, st, own->d_views.p, G);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_tree_ins_leaves, dim3(nblk(k, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, G);
     LAUNCH_CHECK();
     if (n_pad) {
-        hipLaunchKernelGGL(k_tree_ins_pad, dim3(nblk(n_pad, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, G);
+        hipLaunchKernelGGL(k_tree_edit_pad<true>, dim3(nblk(n_pad, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, n_pad, dw + plan.pad_lvl_off, dw + plan.pad_pos_off,
+                           dw /* the pad seed */, pad_ext);
         LAUNCH_CHECK();
     }
     for (int t = 0; t < H; t++) {
         const size_t n = plan.merge[t + 1].size() / 5;
         if (!n) continue;
-        hipLaunchKernelGGL(k_tree_ins_merge, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + plan.merge_off[t + 1],
-                           node_ext + (size_t)(t & 1) * slots * 40, node_ext + (size_t)((t + 1) & 1) * slots * 40, G.pad_ext);
+        hipLaunchKernelGGL(k_tree_edit_merge<true>, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + plan.merge_off[t + 1],
+                           node_ext + (size_t)(t & 1) * slots * 40, node_ext + (size_t)((t + 1) & 1) * slots * 40, pad_ext);
         LAUNCH_CHECK();
     }
     HIPCHK(hipStreamSynchronize(st));
-    own->n_real = 0;
-    own->n_pad = 0;
-    for (int t = 0; t <= H; t++) {
-        own->n_real += own->levels[t].n;
-        if (t < H) own->n_pad += 2 * (uint64_t)own->levels[t + 1].n - own->levels[t].n;
-    }
+    recount_nodes(own);
     poison.armed = false;
     return DAPOL_OK;
 }
@@ -312,8 +320,8 @@ static int32_t tree_remove_incremental(dapol_tree_owned* own, const std::vector<
     uint8_t* d = own->upd_scratch.p;
     HIPCHK(hipMemcpyAsync(d, si.data(), k * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d + o_miss, 0, 8, st));
-    TreeRmFind F{k, H, (const uint64_t*)d, (uint32_t*)(d + o_pos), d + o_hp, (uint32_t*)(d + o_miss)};
-    hipLaunchKernelGGL(k_tree_rm_find, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, F);
+    TreeFind F{k, H, (const uint64_t*)d, (uint32_t*)(d + o_pos), d + o_hp, (uint32_t*)(d + o_miss), nullptr};
+    hipLaunchKernelGGL(k_tree_find_paths, dim3(nblk(k, 64)), dim3(64), 0, st, own->d_views.p, F);
     LAUNCH_CHECK();
     uint32_t missing = 0;
     HIPCHK(hipMemcpyAsync(&missing, d + o_miss, 4, hipMemcpyDeviceToHost, st));
@@ -342,30 +350,26 @@ static int32_t tree_remove_incremental(dapol_tree_owned* own, const std::vector<
     for (int t = 0; t < plan.D; t++)
         losses[t] = RelayoutDel{dw + plan.dead_off[t], (uint32_t)plan.dead[t].size(), dw + plan.dead_off[t + 1], (uint32_t)plan.dead[t + 1].size()};
     StagedLevels staged;
-    { int32_t rc_ = relayout_levels(own, losses, true, staged); if (rc_) return rc_; }
+    RCCHK(relayout_levels(own, losses, true, staged));
     TreePoison poison{own, true};                            // the tree's own state changes from here on
     if (test_knob("DAPOL_TEST_FAIL_REMOVE_MIDWAY")) return fail(DAPOL_ERR_HIP, "injected failure between the compaction and the re-merge (test knob)");
     std::vector<LevelView> hv;
-    { int32_t rc_ = adopt_levels(own, staged, hv); if (rc_) return rc_; }
+    RCCHK(adopt_levels(own, staged, hv));
     // R2: the chain tops' siblings take their padding nodes; R3: the touched survivors, bottom-up
     if (!plan.pad_pos.empty()) {
-        hipLaunchKernelGGL(k_tree_rm_pad, dim3(nblk(plan.pad_pos.size(), 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, plan.pad_pos.size(), d + o_lvl,
-                           dw + plan.pad_off, dw);
+        hipLaunchKernelGGL(k_tree_edit_pad<false>, dim3(nblk(plan.pad_pos.size(), 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, plan.pad_pos.size(),
+                           (const uint8_t*)(d + o_lvl), dw + plan.pad_off, dw /* the pad seed */, (int32_t*)nullptr);
         LAUNCH_CHECK();
     }
     for (int t = 0; t < H; t++) {
         const size_t n = plan.merge[t + 1].size() / 2;
         if (!n) continue;
-        hipLaunchKernelGGL(k_tree_rm_merge, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + plan.merge_off[t + 1]);
+        hipLaunchKernelGGL(k_tree_edit_merge<false>, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + plan.merge_off[t + 1],
+                           (const int32_t*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr);
         LAUNCH_CHECK();
     }
     HIPCHK(hipStreamSynchronize(st));
-    own->n_real = 0;
-    own->n_pad = 0;
-    for (int t = 0; t <= H; t++) {
-        own->n_real += own->levels[t].n;
-        if (t < H) own->n_pad += 2 * (uint64_t)own->levels[t + 1].n - own->levels[t].n;
-    }
+    recount_nodes(own);
     poison.armed = false;
     return DAPOL_OK;
 }

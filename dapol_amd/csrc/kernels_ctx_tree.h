@@ -140,31 +140,6 @@ __global__ void k_ctx_compress(uint32_t* comp /*[rows][8]*/, const int32_t* base
     st8(comp + (size_t)r * 8, c);
 }
 
-// ------------------------------------------------------------------------------------------- commitments
-// DapolNode::new (src/dapol/node.rs:29-45): C = v*B + r*B_blinding, h = BLAKE3(compress(C)).  One lane per node.
-// r: eight words, bit 255 ignored (Scalar::from_bits); may be >= l.
-__global__ __launch_bounds__(256) void k_commit_hash(TableView tbl, size_t n, const uint64_t* v, uint32_t* r, uint32_t* C,
-                                                     uint32_t* H, int32_t* ext) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t rw[8];
-    ld8(rw, r + i * 8);
-    if (rw[7] >> 31) {             // Scalar::from_bits clears bit 255; keep the stored copy consistent
-        rw[7] &= 0x7fffffffu;
-        r[i * 8 + 7] = rw[7];
-    }
-    ge_p3 acc;
-    ge_identity(acc);
-    tbl_fixed_mul_add_u64(acc, tbl, tbl.row_B(0), v[i]);
-    tbl_fixed_mul_add(acc, tbl, tbl.row_Bb(0), rw);
-    uint32_t c[8], h[8];
-    ge_compress(c, acc);
-    node_hash32(tbl.digest, h, c);
-    st8(C + i * 8, c);
-    st8(H + i * 8, h);
-    if (ext) st_p3(ext + i * 40, acc);
-}
-
 // --------------------------------------------------------------------------------------------------- scan
 // The level sizes live on the DEVICE (cnt[k] = real nodes of level k): every kernel of the build reads its bound from there
 // and is launched over the host-side upper bound, so the host never waits for a level (no per-level synchronisation).
@@ -243,6 +218,126 @@ struct LevelView {
     int32_t* ext;   // extended points of this level (only alive while the next level is being built)
 };
 
+// ----------------------------------------------------------------------------------------- node routines
+// What a DAPOL node is, once: every kernel below -- the build, its small-tree phases and the in-place edits -- makes its leaves,
+// padding nodes and parents with these, so that all paths leave the same bytes.
+// Leaf, DapolNode::new (src/dapol/node.rs:29-45): P = v*B + r*B_blinding, c = its encoding, h = D(c).  r: eight words with bit 255
+// already cleared by the caller (Scalar::from_bits); may be >= l.
+__device__ __forceinline__ void leaf_point(ge_p3& P, const TableView& tbl, uint64_t v, const uint32_t* r) {
+    ge_identity(P);
+    tbl_fixed_mul_add_u64(P, tbl, tbl.row_B(0), v);
+    tbl_fixed_mul_add(P, tbl, tbl.row_Bb(0), r);
+}
+__device__ __forceinline__ void leaf_encode(uint32_t* c, uint32_t* h, const TableView& tbl, const ge_p3& P) {
+    ge_compress(c, P);
+    node_hash32(tbl.digest, h, c);
+}
+__device__ __forceinline__ void leaf_node(ge_p3& P, uint32_t* c, uint32_t* h, const TableView& tbl, uint64_t v, const uint32_t* r) {
+    leaf_point(P, tbl, v, r);
+    leaf_encode(c, h, tbl, P);
+}
+// Padding node, Paddable::padding (node.rs:86-88): new(0, r) with r drawn for the node's position (seed mode) or read from the
+// caller's tape.  padding_draw = the positional 64-byte draw; padding_from_wide = the node of a draw: rm / rB = its blinding reduced
+// mod l (Montgomery form / words), pB = rB*B_blinding, cB, hB as for a leaf.
+__device__ __forceinline__ void padding_draw(uint32_t* wide, const uint32_t* pad_seed /*8 words*/, uint64_t level, uint64_t index) {
+    uint32_t seed[8];
+    for (int k = 0; k < 8; k++) seed[k] = pad_seed[k];
+    seed_wide(wide, seed, 1u, level, index);
+}
+__device__ __forceinline__ void padding_from_wide(ge_p3& pB, sc& rm, uint32_t* rB, uint32_t* cB, uint32_t* hB, const TableView& tbl, const uint32_t* wide) {
+    sc_from_wide(rm, wide);
+    sc_from_mont(rB, rm);
+    ge_identity(pB);
+    tbl_fixed_mul_add(pB, tbl, tbl.row_Bb(0), rB);
+    ge_compress(cB, pB);
+    node_hash32(tbl.digest, hB, cB);
+}
+__device__ __forceinline__ void padding_from_wide(ge_p3& pB, uint32_t* rB, uint32_t* cB, uint32_t* hB, const TableView& tbl, const uint32_t* wide) {
+    sc rm;
+    padding_from_wide(pB, rm, rB, cB, hB, tbl, wide);
+}
+__device__ __forceinline__ void padding_node(ge_p3& pB, uint32_t* rB, uint32_t* cB, uint32_t* hB, const TableView& tbl, const uint32_t* pad_seed, uint64_t level,
+                                             uint64_t index) {
+    uint32_t wide[16];
+    padding_draw(wide, pad_seed, level, index);
+    padding_from_wide(pB, rB, cB, hB, tbl, wide);
+}
+// The padding sibling of real node i of level L is kept beside it.
+__device__ __forceinline__ void store_pad_record(const LevelView& L, size_t i, const uint32_t* cB, const uint32_t* hB, const uint32_t* rB) {
+    st8(L.padC + i * 8, cB);
+    st8(L.padH + i * 8, hB);
+    st8(L.padr + i * 8, rB);
+}
+// The other child of the parent of real node c: its padding record, or the real neighbour on its right (c is a left child) or left.
+// rB / vB may be null where a caller has no use for the blinding / the value (a padding node's value is 0).
+__device__ __forceinline__ void load_other_child(uint32_t* cB, uint32_t* hB, uint32_t* rB, uint64_t* vB, const LevelView& L, size_t c, bool left) {
+    if (vB) *vB = 0;
+    if (L.has_pad[c]) {
+        ld8(cB, L.padC + c * 8);
+        ld8(hB, L.padH + c * 8);
+        if (rB) ld8(rB, L.padr + c * 8);
+    } else {
+        const size_t s = left ? c + 1 : c - 1;
+        ld8(cB, L.C + s * 8);
+        ld8(hB, L.H + s * 8);
+        if (rB) ld8(rB, L.r + s * 8);
+        if (vB) *vB = L.v[s];
+    }
+}
+// For a caller that has not read c's index: it is read only where there is a real neighbour to pick.
+__device__ __forceinline__ void load_other_child(uint32_t* cB, uint32_t* hB, uint32_t* rB, uint64_t* vB, const LevelView& L, size_t c) {
+    load_other_child(cB, hB, rB, vB, L, c, L.has_pad[c] || (L.idx[c] & 1ull) == 0);
+}
+// Parent, Mergeable::merge (node.rs:64-80): r = (r_A + r_B) mod l (dalek's Scalar add reduces even unreduced inputs), P = P_A + P_B,
+// h = D(C_L || C_R || H_L || H_R) with A on the left or on the right.  (v = v_A + v_B with u64 wrap is the caller's one addition.)
+__device__ __forceinline__ void sc_add_words(uint32_t* rp, const uint32_t* rA, const uint32_t* rB) {
+    sc ma, mb, ms;
+    sc_to_mont(ma, rA);
+    sc_to_mont(mb, rB);
+    sc_add(ms, ma, mb);
+    sc_from_mont(rp, ms);
+}
+__device__ __forceinline__ void parent_hash(int digest, uint32_t* hp, bool a_is_left, const uint32_t* cA, const uint32_t* cB, const uint32_t* hA, const uint32_t* hB) {
+    if (a_is_left) node_hash128(digest, hp, cA, cB, hA, hB);
+    else node_hash128(digest, hp, cB, cA, hB, hA);
+}
+__device__ __forceinline__ void merge_parent(ge_p3& pp, uint32_t* rp, uint32_t* cp, uint32_t* hp, int digest, bool a_is_left, const ge_p3& pA, const ge_p3& pB,
+                                             const uint32_t* rA, const uint32_t* rB, const uint32_t* cA, const uint32_t* cB, const uint32_t* hA, const uint32_t* hB) {
+    sc_add_words(rp, rA, rB);
+    ge_add(pp, pA, pB);
+    ge_compress(cp, pp);
+    parent_hash(digest, hp, a_is_left, cA, cB, hA, hB);
+}
+// Lower bound of `want` in the sorted idx[0 .. n).
+__device__ __forceinline__ size_t lower_bound_u64(const uint64_t* idx, size_t n, uint64_t want) {
+    size_t lo = 0, hi = n;
+    while (lo < hi) {
+        const size_t mid = (lo + hi) >> 1;
+        if (idx[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// ------------------------------------------------------------------------------------------- commitments
+// One lane per node: leaf_node of (v[i], r[i]); bit 255 of r is ignored.
+__global__ __launch_bounds__(256) void k_commit_hash(TableView tbl, size_t n, const uint64_t* v, uint32_t* r, uint32_t* C,
+                                                     uint32_t* H, int32_t* ext) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t rw[8];
+    ld8(rw, r + i * 8);
+    if (rw[7] >> 31) {             // Scalar::from_bits clears bit 255; keep the stored copy consistent
+        rw[7] &= 0x7fffffffu;
+        r[i * 8 + 7] = rw[7];
+    }
+    ge_p3 acc;
+    uint32_t c[8], h[8];
+    leaf_node(acc, c, h, tbl, v[i], rw);
+    st8(C + i * 8, c);
+    st8(H + i * 8, h);
+    if (ext) st_p3(ext + i * 40, acc);
+}
+
 // One lane per PARENT q (smtree build restated level-synchronously): children = the real node head[q] and either
 // the adjacent real node or a padding node made on the spot (Paddable::padding, src/dapol/node.rs:86-88, with the
 // positional seed-mode blinding); parent = Mergeable::merge (node.rs:64-80).
@@ -291,42 +386,23 @@ __global__ __launch_bounds__(256) void k_tree_merge(TableView tbl, LevelView cur
         ld_p3(pB, extpad + q * 40);
         cur.has_pad[i] = 1;
     } else {
-        uint32_t seed[8], wide[16];
+        uint32_t wide[16];
         if (tape.draws) {
             uint64_t rank = 2 * (uint64_t)q - (uint64_t)i;
             for (int j = 0; j < level; j++) rank += 2 * (uint64_t)cnt[j + 1] - (uint64_t)cnt[j];
             if (rank < tape.n_draws) { for (int k = 0; k < 16; k++) wide[k] = tape.draws[rank * 16 + k]; }
             else { atomicOr(tape.short_flag, 1u); for (int k = 0; k < 16; k++) wide[k] = 0; }
         } else {
-            for (int k = 0; k < 8; k++) seed[k] = pad_seed[k];
-            seed_wide(wide, seed, 1u, (uint64_t)level, my_idx ^ 1ull);
+            padding_draw(wide, pad_seed, (uint64_t)level, my_idx ^ 1ull);
         }
-        sc rm;
-        sc_from_wide(rm, wide);
-        sc_from_mont(rB, rm);
-        ge_identity(pB);
-        tbl_fixed_mul_add(pB, tbl, tbl.row_Bb(0), rB);
-        ge_compress(cB, pB);
-        node_hash32(tbl.digest, hB, cB);
-        st8(cur.padC + i * 8, cB);
-        st8(cur.padH + i * 8, hB);
-        st8(cur.padr + i * 8, rB);
+        padding_from_wide(pB, rB, cB, hB, tbl, wide);
+        store_pad_record(cur, i, cB, hB, rB);
         cur.has_pad[i] = 1;
     }
     cur.parent[i] = (uint32_t)q;
-    bool a_is_left = pair || ((my_idx & 1ull) == 0);
-    // r = (r_L + r_R) mod l  (dalek Scalar add reduces even unreduced inputs)
-    sc ma, mb, ms;
-    sc_to_mont(ma, rA);
-    sc_to_mont(mb, rB);
-    sc_add(ms, ma, mb);
     uint32_t rp[8], cp[8], hp[8];
-    sc_from_mont(rp, ms);
     ge_p3 pp;
-    ge_add(pp, pA, pB);
-    ge_compress(cp, pp);
-    if (a_is_left) node_hash128(tbl.digest, hp, cA, cB, hA, hB);
-    else node_hash128(tbl.digest, hp, cB, cA, hB, hA);
+    merge_parent(pp, rp, cp, hp, tbl.digest, pair || ((my_idx & 1ull) == 0), pA, pB, rA, rB, cA, cB, hA, hB);
     nxt.idx[q] = my_idx >> 1;
     nxt.v[q] = vA + vB;           // u64 wrap == release-mode Rust (node.rs:72)
     st8(nxt.r + q * 8, rp);
@@ -344,39 +420,21 @@ __global__ __launch_bounds__(256) void k_tree_pad_level(TableView tbl, LevelView
     size_t i = head[q];
     uint64_t my_idx = cur.idx[i];
     if ((i + 1 < cur_n) && (cur.idx[i + 1] == (my_idx ^ 1ull))) return;
-    uint32_t seed[8], wide[16], rB[8], cB[8], hB[8];
-    for (int k = 0; k < 8; k++) seed[k] = pad_seed[k];
-    seed_wide(wide, seed, 1u, (uint64_t)level, my_idx ^ 1ull);
-    sc rm;
-    sc_from_wide(rm, wide);
-    sc_from_mont(rB, rm);
+    uint32_t rB[8], cB[8], hB[8];
     ge_p3 pB;
-    ge_identity(pB);
-    tbl_fixed_mul_add(pB, tbl, tbl.row_Bb(0), rB);
-    ge_compress(cB, pB);
-    node_hash32(tbl.digest, hB, cB);
-    st8(cur.padC + i * 8, cB);
-    st8(cur.padH + i * 8, hB);
-    st8(cur.padr + i * 8, rB);
+    padding_node(pB, rB, cB, hB, tbl, pad_seed, (uint64_t)level, my_idx ^ 1ull);
+    store_pad_record(cur, i, cB, hB, rB);
     st_p3(extpad + q * 40, pB);
 }
 
-// Paddable::padding (src/dapol/node.rs:86-88): new(0, random blinding) with the draw keyed by the node's position.
+// The padding nodes of n given positions (level[i], index[i]), as records.
 __global__ void k_padding_nodes(TableView tbl, size_t n, const uint32_t* pad_seed, const uint8_t* level, const uint64_t* index, uint32_t* C,
                                 uint32_t* H, uint32_t* r) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    uint32_t seed[8], wide[16], rB[8], cB[8], hB[8];
-    for (int k = 0; k < 8; k++) seed[k] = pad_seed[k];
-    seed_wide(wide, seed, 1u, (uint64_t)level[i], index[i]);
-    sc rm;
-    sc_from_wide(rm, wide);
-    sc_from_mont(rB, rm);
+    uint32_t rB[8], cB[8], hB[8];
     ge_p3 p;
-    ge_identity(p);
-    tbl_fixed_mul_add(p, tbl, tbl.row_Bb(0), rB);
-    ge_compress(cB, p);
-    node_hash32(tbl.digest, hB, cB);
+    padding_node(p, rB, cB, hB, tbl, pad_seed, (uint64_t)level[i], index[i]);
     st8(C + i * 8, cB);
     st8(H + i * 8, hB);
     st8(r + i * 8, rB);
@@ -391,7 +449,7 @@ __global__ void k_padding_nodes(TableView tbl, size_t n, const uint32_t* pad_see
 // -- and every ancestor is independent of every other, so all levels run side by side (U2); only the hash chain is sequential
 // over the levels (U3, one block stepping through them).  The result equals dapol_tree_build over the new leaf set bit for bit
 // (ristretto encodings are canonical; tests/test_gpu_parity.py::test_update_equals_build).
-//   U0  k_tree_upd_find     per update: find the leaf and its node positions at every level (parent pointers); a missing index
+//   U0  k_tree_find_paths   per update: find the leaf and its node positions at every level (parent pointers); a missing index
 //                           sends the whole batch to the rebuild before anything has been written
 //   U1  k_tree_upd_leaves   per update: the leaf's new node, dP = P_new - P_old, dv, dr
 //   U2  k_tree_upd_nodes    per (update, level >= 1): the first update of a run that shares the node adds the run's deltas to it
@@ -406,27 +464,41 @@ struct TreeUpdArgs {
     int32_t* dP;               // [k][40]           P_new - P_old, extended
     uint64_t* dv;              // [k]
     uint32_t* dr;              // [k][8]            Montgomery form
-    uint32_t* missing;         // != 0: some leaf index is not in the tree (the caller rebuilds instead)
+    uint32_t* missing;         // U0's outputs (TreeFind): != 0: some leaf index is not in the tree (the caller rebuilds instead)
     uint8_t* found;            // [k] (may be null): per update, whether its leaf exists
     const uint32_t* first;     // [k] (may be null = 1): lowest level whose EXISTING node this update changes by its delta
 };
-// U0: where the updated leaves are (nothing is written to the tree until every index has been found)
-__global__ __launch_bounds__(64) void k_tree_upd_find(const LevelView* views, TreeUpdArgs U) {
+// U0 (and R0 of the removal): where the edited leaves are, before anything is written to the tree.  The optional outputs are null
+// where a path has no use for them.
+struct TreeFind {
+    size_t k;
+    int height;
+    const uint64_t* idx;       // [k] sorted, distinct
+    uint32_t* pos;             // [k][height + 1] node position at every level (parent pointers)
+    uint8_t* has_pad;          // [k][height + 1] (may be null): has_pad of that node
+    uint32_t* missing;         // != 0: some index is not a leaf of the tree
+    uint8_t* found;            // [k] (may be null): per index, whether its leaf exists
+};
+__global__ __launch_bounds__(64) void k_tree_find_paths(const LevelView* views, TreeFind F) {
     const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (j >= U.k) return;
+    if (j >= F.k) return;
     const LevelView L0 = views[0];
-    const uint64_t want = U.idx[j];
-    size_t lo = 0, hi = L0.n;                       // lower bound in the sorted leaf indexes
-    while (lo < hi) {
-        const size_t mid = (lo + hi) >> 1;
-        if (L0.idx[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= L0.n || L0.idx[lo] != want) { atomicOr(U.missing, 1u); if (U.found) U.found[j] = 0; return; }
-    if (U.found) U.found[j] = 1;
-    uint32_t* pos = U.pos + j * (size_t)(U.height + 1);
+    const uint64_t want = F.idx[j];
+    const size_t lo = lower_bound_u64(L0.idx, L0.n, want);
+    const bool found = lo < L0.n && L0.idx[lo] == want;
+    if (F.found) F.found[j] = found ? 1 : 0;
+    if (!found) { atomicOr(F.missing, 1u); return; }
+    const size_t stride = (size_t)F.height + 1;
+    uint32_t* pos = F.pos + j * stride;
+    uint8_t* hp = F.has_pad ? F.has_pad + j * stride : nullptr;
     size_t p = lo;
-    pos[0] = (uint32_t)p;
-    for (int k = 0; k < U.height; k++) { p = views[k].parent[p]; pos[k + 1] = (uint32_t)p; }
+    for (int t = 0; t < F.height; t++) {
+        pos[t] = (uint32_t)p;
+        if (hp) hp[t] = views[t].has_pad[p];
+        p = views[t].parent[p];
+    }
+    pos[F.height] = (uint32_t)p;
+    if (hp) hp[F.height] = 0;
 }
 __global__ __launch_bounds__(64) void k_tree_upd_leaves(TableView tbl, const LevelView* views, TreeUpdArgs U) {
     const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -439,9 +511,7 @@ __global__ __launch_bounds__(64) void k_tree_upd_leaves(TableView tbl, const Lev
     ld8(ro, L0.r + lo * 8);
     ld8(c, L0.C + lo * 8);
     ge_p3 pn, po, npo, d;
-    ge_identity(pn);
-    tbl_fixed_mul_add_u64(pn, tbl, tbl.row_B(0), U.v[j]);
-    tbl_fixed_mul_add(pn, tbl, tbl.row_Bb(0), rn);
+    leaf_point(pn, tbl, U.v[j], rn);
     (void)ge_decompress(po, c);                    // the tree's own encoding: always decodes
     ge_neg(npo, po);
     ge_add(d, pn, npo);
@@ -452,8 +522,7 @@ __global__ __launch_bounds__(64) void k_tree_upd_leaves(TableView tbl, const Lev
     sc_sub(md, mn, mo);
     for (int i = 0; i < 8; i++) U.dr[j * 8 + i] = md.v[i];
     U.dv[j] = U.v[j] - L0.v[lo];
-    ge_compress(c, pn);
-    node_hash32(tbl.digest, h, c);
+    leaf_encode(c, h, tbl, pn);                    // (after the delta: the old encoding's words are free by now)
     L0.v[lo] = U.v[j];
     st8(L0.r + lo * 8, rn);
     st8(L0.C + lo * 8, c);
@@ -511,10 +580,8 @@ __global__ __launch_bounds__(1024) void k_tree_upd_hash(int digest, const LevelV
                 uint32_t cA[8], hA[8], cB[8], hB[8], hp[8];
                 ld8(cA, L.C + i * 8); ld8(hA, L.H + i * 8);
                 const bool left = (my & 1ull) == 0;
-                if (L.has_pad[i]) { ld8(cB, L.padC + i * 8); ld8(hB, L.padH + i * 8); }
-                else { const size_t s = left ? i + 1 : i - 1; ld8(cB, L.C + s * 8); ld8(hB, L.H + s * 8); }
-                if (left) node_hash128(digest, hp, cA, cB, hA, hB);
-                else node_hash128(digest, hp, cB, cA, hB, hA);
+                load_other_child(cB, hB, nullptr, nullptr, L, i, left);
+                parent_hash(digest, hp, left, cA, cB, hA, hB);
                 st8(views[k + 1].H + (size_t)pp * 8, hp);
             }
         }
@@ -530,11 +597,11 @@ __global__ __launch_bounds__(1024) void k_tree_upd_hash(int digest, const LevelV
 // dv = v.  The level arrays are compact and sorted, so a level that gains nodes is rewritten out of place (k_tree_relayout: every
 // existing node moves up by the number of insertions before it, parent pointers follow the next level's moves); no commitment is
 // recomputed for it.  Leaves whose new chains would share a node (two new leaves under one new subtree) are left to the rebuild.
-//   I1  k_tree_ins_plan   per new leaf: chain length m, insertion position at every level below m, position of the first
-//                         existing ancestor; flags chains that share a node
-//   I2  k_tree_relayout   per level that gains nodes: the level's arrays in their new order (existing nodes only)
-//   I3  k_tree_ins_chain  a wavefront per new leaf, lane t = chain node t: padding siblings, prefix sums of their points,
-//                         encodings; writes the new nodes, drops S's padding sibling, leaves the delta for the levels above
+//   I1  k_tree_ins_plan<1>  per new leaf: chain length m, insertion position at every level below m, position of the first
+//                           existing ancestor; flags chains that share a node
+//   I2  k_tree_relayout     per level that gains nodes: the level's arrays in their new order (existing nodes only)
+//   I3  k_tree_ins_chain    a wavefront per new leaf, lane t = chain node t: padding siblings, prefix sums of their points,
+//                           encodings; writes the new nodes, drops S's padding sibling, leaves the delta for the levels above
 //   then U2 / U3 of the replacement path (k_tree_upd_nodes from level m, k_tree_upd_hash from the leaves).
 struct TreeInsPlan {
     size_t k;
@@ -542,27 +609,30 @@ struct TreeInsPlan {
     const uint64_t* idx;       // [k] sorted, distinct, all NEW
     uint32_t* m;               // [k] chain length (1..height)
     uint32_t* inspos;          // [k][height + 1]: t < m: lower-bound position in level t (old layout); [m]: position of the existing ancestor
-    uint32_t* conflict;        // != 0: two chains share a new node
+    uint32_t* conflict;        // bit 1: two chains share a new node; bit 2: an index is a leaf already
 };
+// STOP = true (I1): the search ends at the first existing ancestor, inspos[j][t] is written for t <= m.  STOP = false (J1 of the general
+// insert, below): continued to the root, inspos[j][t] is written for every t <= height.
+template <bool STOP>
 __global__ __launch_bounds__(64) void k_tree_ins_plan(const LevelView* views, TreeInsPlan P) {
     const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (j >= P.k) return;
     const uint64_t x = P.idx[j];
     uint32_t* out = P.inspos + j * (size_t)(P.height + 1);
-    int m = P.height;
+    int m = -1;
     for (int t = 0; t <= P.height; t++) {
         const LevelView L = views[t];
         const uint64_t want = t < 64 ? x >> t : 0;
-        size_t lo = 0, hi = L.n;
-        while (lo < hi) {
-            const size_t mid = (lo + hi) >> 1;
-            if (L.idx[mid] < want) lo = mid + 1; else hi = mid;
-        }
+        const size_t lo = lower_bound_u64(L.idx, L.n, want);
         out[t] = (uint32_t)lo;
-        if (lo < L.n && L.idx[lo] == want) { m = t; break; }
+        if (m < 0 && lo < L.n && L.idx[lo] == want) {
+            m = t;
+            if (STOP) break;
+        }
     }
+    if (m < 0) m = P.height;
     P.m[j] = (uint32_t)m;
-    if (m == 0) atomicOr(P.conflict, 2u);          // (the leaf exists: the caller partitions wrongly)
+    if (m == 0) atomicOr(P.conflict, 2u);          // the leaf exists already
     if (j > 0) {                                    // shares a new node with its left neighbour?
         const uint64_t y = P.idx[j - 1];
         for (int t = 0; t < m; t++)
@@ -627,12 +697,10 @@ __global__ __launch_bounds__(64) void k_tree_ins_chain(TableView tbl, const Leve
     ld8(rl, I.r + j * 8);
     rl[7] &= 0x7fffffffu;                          // Scalar::from_bits
     ge_p3 P0;
-    ge_identity(P0);
-    tbl_fixed_mul_add_u64(P0, tbl, tbl.row_B(0), I.v[j]);
-    tbl_fixed_mul_add(P0, tbl, tbl.row_Bb(0), rl);
+    leaf_point(P0, tbl, I.v[j], rl);
     sc r0;
     sc_to_mont(r0, rl);
-    // lane t: the padding sibling of chain node t (needed for t < m - 1), Paddable::padding at (t, (x >> t) ^ 1)
+    // lane t: the padding sibling of chain node t (needed for t < m - 1), the padding node at (t, (x >> t) ^ 1)
     const bool has_pad = t < m - 1;
     ge_p3 Pp;
     ge_identity(Pp);
@@ -640,14 +708,9 @@ __global__ __launch_bounds__(64) void k_tree_ins_chain(TableView tbl, const Leve
     sc_zero(rp);
     uint32_t rB[8] = {0}, cB[8] = {0}, hB[8] = {0};
     if (has_pad) {
-        uint32_t seed[8], wide[16];
-        for (int q = 0; q < 8; q++) seed[q] = I.pad_seed[q];
-        seed_wide(wide, seed, 1u, (uint64_t)t, (x >> t) ^ 1ull);
-        sc_from_wide(rp, wide);
-        sc_from_mont(rB, rp);
-        tbl_fixed_mul_add(Pp, tbl, tbl.row_Bb(0), rB);
-        ge_compress(cB, Pp);
-        node_hash32(tbl.digest, hB, cB);
+        uint32_t wide[16];
+        padding_draw(wide, I.pad_seed, (uint64_t)t, (x >> t) ^ 1ull);
+        padding_from_wide(Pp, rp, rB, cB, hB, tbl, wide);
     }
     // inclusive prefix sums over the lanes: S_t = sum_{u <= t} pad(u) (points and blindings); chain node t = leaf + S_{t-1}
     ge_p3 S = Pp;
@@ -685,7 +748,7 @@ __global__ __launch_bounds__(64) void k_tree_ins_chain(TableView tbl, const Leve
     st8(L.C + d * 8, cN);
     if (t == 0) { node_hash32(tbl.digest, hN, cN); st8(L.H + d * 8, hN); }       // (parents' hashes: k_tree_upd_hash, level by level)
     L.has_pad[d] = has_pad ? 1 : 0;
-    if (has_pad) { st8(L.padC + d * 8, cB); st8(L.padH + d * 8, hB); st8(L.padr + d * 8, rB); }
+    if (has_pad) store_pad_record(L, d, cB, hB, rB);
     L.parent[d] = np[t + 1];
     uint32_t* pos = I.pos + j * (size_t)(I.height + 1);
     pos[t] = (uint32_t)d;
@@ -718,60 +781,27 @@ __global__ __launch_bounds__(64) void k_tree_ins_chain(TableView tbl, const Leve
 // the wavefront-per-chain prefix sums of I3 cannot express.  It is the removal's mirror image: the host plans the forest
 // (plan_insert_general), the levels that gain nodes are rewritten by k_tree_relayout, and every FRESH node -- a new one, or an existing
 // ancestor of a new leaf -- is merged from its children level by level, bottom-up.
-//   J1  k_tree_ins_plan_all  per new leaf: as I1, continued to the root: the lower bound of x >> t at EVERY level
-//   J2  k_tree_relayout      per level that gains nodes (existing nodes only)
-//   J3  k_tree_ins_struct    per new node: idx, parent, has_pad = 0; a chain top also clears has_pad of its real sibling S
-//   J4  k_tree_ins_leaves    per new leaf: v*B + r*B_blinding, its record, its extended point
-//   J5  k_tree_ins_pad       per new node with a padding sibling: k_tree_rm_pad's record, and its extended point
-//   J6  k_tree_ins_merge     per level: every fresh node = Mergeable::merge of its children
+//   J1  k_tree_ins_plan<0>    per new leaf: as I1, continued to the root: the lower bound of x >> t at EVERY level
+//   J2  k_tree_relayout       per level that gains nodes (existing nodes only)
+//   J3  k_tree_ins_struct     per new node: idx, parent, has_pad = 0; a chain top also clears has_pad of its real sibling S
+//   J4  k_tree_ins_leaves     per new leaf: its node, its extended point
+//   J5  k_tree_edit_pad<1>    per new node with a padding sibling: the padding node's record, and its extended point
+//   J6  k_tree_edit_merge<1>  per level: every fresh node = the parent of its children
 // A point this call has produced is never decoded again: J4 - J6 leave the extended point of every fresh node and every new padding
 // node in the call's scratch (160 bytes a slot; node slots alternate between two halves by level parity), and a merge reads a child
 // made by this call from there.  Only an untouched existing sibling, or an existing padding record, is decoded from its 32 bytes.
-// On the private part of a new chain both children are fresh, so a merge pays one encoding and no decoding -- k_tree_rm_merge pays
+// On the private part of a new chain both children are fresh, so a merge pays one encoding and no decoding -- the removal's merge pays
 // two decodings and an encoding, each an inverse square root, on what is a serial chain of single-lane launches for a small batch.
-// Compiler report, gfx950 (VGPRs / scratch bytes a lane): k_tree_ins_plan_all 36 / 0; k_tree_ins_struct 22 / 0; k_tree_ins_leaves
-// 178 / 448; k_tree_ins_pad 188 / 448; k_tree_ins_merge 226 / 624 (k_tree_rm_merge: 186 / 800) -- two waves a SIMD for the three that
-// hold a point, which a launch of a few lanes does not notice and a launch of thousands shares with the build's own kernels.
-// J1: k_tree_ins_plan (same arguments) that does not stop at the first existing ancestor: inspos[j][t] is written for every t <= height.
-// (It searches every level; above m the parent pointers would give the same positions for one load a level -- not done yet, see
-// DESIGN.md 4.3 on the 0.1 ms this costs a small batch.)
-// conflict bit 1 (chains that share a node) only selects the path here; bit 2 = an index that is a leaf already.
-__global__ __launch_bounds__(64) void k_tree_ins_plan_all(const LevelView* views, TreeInsPlan P) {
-    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (j >= P.k) return;
-    const uint64_t x = P.idx[j];
-    uint32_t* out = P.inspos + j * (size_t)(P.height + 1);
-    int m = -1;
-    for (int t = 0; t <= P.height; t++) {
-        const LevelView L = views[t];
-        const uint64_t want = t < 64 ? x >> t : 0;
-        size_t lo = 0, hi = L.n;
-        while (lo < hi) {
-            const size_t mid = (lo + hi) >> 1;
-            if (L.idx[mid] < want) lo = mid + 1; else hi = mid;
-        }
-        out[t] = (uint32_t)lo;
-        if (m < 0 && lo < L.n && L.idx[lo] == want) m = t;
-    }
-    if (m < 0) m = P.height;
-    P.m[j] = (uint32_t)m;
-    if (m == 0) atomicOr(P.conflict, 2u);          // the leaf exists
-    if (j > 0) {                                    // shares a new node with its left neighbour?
-        const uint64_t y = P.idx[j - 1];
-        for (int t = 0; t < m; t++)
-            if ((t < 64 ? x >> t : 0) == (t < 64 ? y >> t : 0)) { atomicOr(P.conflict, 1u); break; }
-    }
-}
+// Compiler report, gfx950: profiles/tree_node_routines.txt -- two waves a SIMD for the kernels that hold a point, which a launch of a
+// few lanes does not notice and a launch of thousands shares with the build's own kernels.
+// (J1 searches every level; above m the parent pointers would give the same positions for one load a level -- not done yet, see
+// DESIGN.md 4.3 on the 0.1 ms this costs a small batch.)  conflict bit 1 (chains that share a node) only selects the path here.
 struct TreeInsGeneral {
-    size_t n_new, k, n_pad;
+    size_t n_new, k;
     const uint32_t *lvl, *pos, *parent, *sib, *idx_lo, *idx_hi;    // [n_new]: the new nodes (plan_insert_general's n_*)
     const uint32_t* leaf_pos;                                       // [k]
-    const uint32_t *pad_lvl, *pad_pos;                              // [n_pad]
     const uint64_t* v; const uint32_t* r;                           // [k], [k][8]: the new leaves, sorted by index
-    const uint32_t* pad_seed;                                       // [8]
     int32_t* node_ext;                                              // [2][slots][40]: fresh nodes, half = level & 1
-    int32_t* pad_ext;                                               // [n_pad][40]
-    uint32_t slots;
 };
 // J3
 __global__ __launch_bounds__(64) void k_tree_ins_struct(const LevelView* views, TreeInsGeneral G) {
@@ -794,81 +824,67 @@ __global__ __launch_bounds__(64) void k_tree_ins_leaves(TableView tbl, const Lev
     ld8(rl, G.r + j * 8);
     rl[7] &= 0x7fffffffu;                          // Scalar::from_bits; the leaf keeps its blinding as given (possibly >= l)
     ge_p3 P0;
-    ge_identity(P0);
-    tbl_fixed_mul_add_u64(P0, tbl, tbl.row_B(0), G.v[j]);
-    tbl_fixed_mul_add(P0, tbl, tbl.row_Bb(0), rl);
-    ge_compress(c, P0);
-    node_hash32(tbl.digest, h, c);
+    leaf_node(P0, c, h, tbl, G.v[j], rl);
     L.v[d] = G.v[j];
     st8(L.r + d * 8, rl);
     st8(L.C + d * 8, c);
     st8(L.H + d * 8, h);
     st_p3(G.node_ext + j * 40, P0);
 }
-// J5: k_tree_rm_pad for the new node at (pad_lvl[i], pad_pos[i]), which also keeps the padding node's extended point.
-__global__ __launch_bounds__(64) void k_tree_ins_pad(TableView tbl, const LevelView* views, TreeInsGeneral G) {
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= G.n_pad) return;
-    const int t = (int)G.pad_lvl[i];
-    const size_t s = G.pad_pos[i];
-    const LevelView L = views[t];
-    uint32_t seed[8], wide[16], rB[8], cB[8], hB[8];
-    for (int k = 0; k < 8; k++) seed[k] = G.pad_seed[k];
-    seed_wide(wide, seed, 1u, (uint64_t)t, L.idx[s] ^ 1ull);
-    sc rm;
-    sc_from_wide(rm, wide);
-    sc_from_mont(rB, rm);
-    ge_p3 pB;
-    ge_identity(pB);
-    tbl_fixed_mul_add(pB, tbl, tbl.row_Bb(0), rB);
-    ge_compress(cB, pB);
-    node_hash32(tbl.digest, hB, cB);
-    st8(L.padC + s * 8, cB);
-    st8(L.padH + s * 8, hB);
-    st8(L.padr + s * 8, rB);
-    L.has_pad[s] = 1;
-    st_p3(G.pad_ext + i * 40, pB);
-}
-// J6, one level: e[5 i ..] = position of a fresh node in nxt | position of its first fresh child in cur | the node's slot | the
-// child's slot | the other child: a slot of cur's half, 0x80000000 | pad slot, or 0xffffffff = decode it.  The pairing, the hash
-// order, the u64 wrap and r mod l are k_tree_rm_merge's.
-__global__ __launch_bounds__(64) void k_tree_ins_merge(int digest, LevelView cur, LevelView nxt, size_t n, const uint32_t* e, const int32_t* ext_cur,
-                                                       int32_t* ext_nxt, const int32_t* pad_ext) {
+// J5 and R2 of the removal (below): real node pos[i] of level level[i] gains its padding sibling.  KEEP_EXT: the padding node's
+// extended point stays in ext[i] for the merges above it.  LevelT is deduced from the plan's level list -- bytes in the removal's, words
+// in the insert's -- so the two instantiations the stage lists call <0> and <1> are <false, uint8_t> and <true, uint32_t> in the code object.
+template <bool KEEP_EXT, typename LevelT>
+__global__ __launch_bounds__(64) void k_tree_edit_pad(TableView tbl, const LevelView* views, size_t n, const LevelT* level, const uint32_t* pos,
+                                                      const uint32_t* pad_seed, int32_t* ext) {
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    const size_t p = e[5 * i], c = e[5 * i + 1];
-    const uint32_t slot_p = e[5 * i + 2], slot_c = e[5 * i + 3], other = e[5 * i + 4];
+    const int t = (int)level[i];
+    const size_t s = pos[i];
+    const LevelView L = views[t];
+    uint32_t rB[8], cB[8], hB[8];
+    ge_p3 pB;
+    padding_node(pB, rB, cB, hB, tbl, pad_seed, (uint64_t)t, L.idx[s] ^ 1ull);
+    store_pad_record(L, s, cB, hB, rB);
+    L.has_pad[s] = 1;
+    if (KEEP_EXT) st_p3(ext + i * 40, pB);
+}
+// J6 and R3 of the removal, one level: a record of e per node of nxt to make again from its children in cur (new layout): the node's
+// position | the position of one of its children; the other child is that child's padding record or real neighbour, as k_tree_merge
+// pairs them.  SLOTS = false (removal, 2 words a record): both children's points are decoded from their encodings, which are the
+// tree's own and always decode.  SLOTS = true (insert, 5 words): | the node's slot | the child's slot | the other child: a slot of
+// cur's half, 0x80000000 | pad slot, or 0xffffffff = decode it; the node's point is left in its slot.
+template <bool SLOTS>
+__global__ __launch_bounds__(64) void k_tree_edit_merge(int digest, LevelView cur, LevelView nxt, size_t n, const uint32_t* e, const int32_t* ext_cur,
+                                                        int32_t* ext_nxt, const int32_t* pad_ext) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* rec = e + (SLOTS ? 5 : 2) * i;
+    const size_t p = rec[0], c = rec[1];
     const bool left = (cur.idx[c] & 1ull) == 0;
     uint32_t cA[8], hA[8], rA[8], cB[8], hB[8], rB[8];
     const uint64_t vA = cur.v[c];
-    uint64_t vB = 0;
+    uint64_t vB;
     ld8(cA, cur.C + c * 8); ld8(hA, cur.H + c * 8); ld8(rA, cur.r + c * 8);
-    if (cur.has_pad[c]) { ld8(cB, cur.padC + c * 8); ld8(hB, cur.padH + c * 8); ld8(rB, cur.padr + c * 8); }
-    else {
-        const size_t s = left ? c + 1 : c - 1;
-        ld8(cB, cur.C + s * 8); ld8(hB, cur.H + s * 8); ld8(rB, cur.r + s * 8);
-        vB = cur.v[s];
-    }
+    load_other_child(cB, hB, rB, &vB, cur, c, left);
     ge_p3 pA, pB, pp;
-    ld_p3(pA, ext_cur + (size_t)slot_c * 40);
-    if (other == 0xffffffffu) (void)ge_decompress(pB, cB);          // the tree's own encoding: always decodes
-    else if (other & 0x80000000u) ld_p3(pB, pad_ext + (size_t)(other & 0x7fffffffu) * 40);
-    else ld_p3(pB, ext_cur + (size_t)other * 40);
-    ge_add(pp, pA, pB);
-    sc ma, mb, ms;
-    sc_to_mont(ma, rA);
-    sc_to_mont(mb, rB);
-    sc_add(ms, ma, mb);
+    if (SLOTS) {
+        const uint32_t other = rec[4];
+        ld_p3(pA, ext_cur + (size_t)rec[3] * 40);
+        if (other == 0xffffffffu) (void)ge_decompress(pB, cB);
+        else if (other & 0x80000000u) ld_p3(pB, pad_ext + (size_t)(other & 0x7fffffffu) * 40);
+        else ld_p3(pB, ext_cur + (size_t)other * 40);
+    } else {
+        (void)ge_decompress(pA, cA);
+        (void)ge_decompress(pB, cB);
+    }
     uint32_t rp[8], cp[8], hp[8];
-    sc_from_mont(rp, ms);
-    ge_compress(cp, pp);
-    if (left) node_hash128(digest, hp, cA, cB, hA, hB);
-    else node_hash128(digest, hp, cB, cA, hB, hA);
+    merge_parent(pp, rp, cp, hp, digest, left, pA, pB, rA, rB, cA, cB, hA, hB);
     nxt.v[p] = vA + vB;                            // u64 wrap == release-mode Rust (node.rs:72)
     st8(nxt.r + p * 8, rp);
     st8(nxt.C + p * 8, cp);
     st8(nxt.H + p * 8, hp);
-    st_p3(ext_nxt + (size_t)slot_p * 40, pp);
+    if (SLOTS) st_p3(ext_nxt + (size_t)rec[2] * 40, pp);
 }
 
 // ------------------------------------------------------------------------------------- incremental remove
@@ -878,100 +894,14 @@ __global__ __launch_bounds__(64) void k_tree_ins_merge(int digest, LevelView cur
 // the top's position (level t, idx_S ^ 1) -- the very draw k_tree_pad_level makes for it.  Padding records of dead nodes go with
 // them; a survivor never loses has_pad.  Chains may share nodes (two sibling leaves, a whole subtree): the host finds the dead
 // nodes and the touched survivors level by level from R0's positions, and every touched survivor is merged again from its children.
-//   R0  k_tree_rm_find     per removed leaf: its node position and has_pad flag at every level (parent pointers); a missing index
-//                          reports DAPOL_ERR_UNKNOWN_LEAF before anything has been written
-//   R1  k_tree_relayout    per level that loses nodes: the survivors, compacted (with the deletions of RelayoutDel)
-//   R2  k_tree_rm_pad      per chain top: S's new padding sibling
-//   R3  k_tree_rm_merge    per level, bottom-up: every touched survivor = Mergeable::merge of its children, as k_tree_merge makes it
+//   R0  k_tree_find_paths     per removed leaf: its node position and has_pad flag at every level (parent pointers); a missing index
+//                             reports DAPOL_ERR_UNKNOWN_LEAF before anything has been written
+//   R1  k_tree_relayout       per level that loses nodes: the survivors, compacted (with the deletions of RelayoutDel)
+//   R2  k_tree_edit_pad<0>    per chain top: S's new padding sibling (level / pos = level and new position of S)
+//   R3  k_tree_edit_merge<0>  per level, bottom-up: every touched survivor = the parent of its children, as k_tree_merge makes it
 // A survivor is re-merged rather than moved by a delta: the parent of a chain top may also change through removals under S, and
 // chain tops sit at different levels, so the deltas of one ancestor would have to be gathered across chains; a merge reads what
 // is already there (children of the level below, the padding records of R2) and needs no bookkeeping between chains.
-struct TreeRmFind {
-    size_t k;
-    int height;
-    const uint64_t* idx;       // [k] sorted, distinct
-    uint32_t* pos;             // [k][height + 1] node position at every level (old layout)
-    uint8_t* has_pad;          // [k][height + 1] has_pad of that node
-    uint32_t* missing;         // != 0: some index is not a leaf of the tree
-};
-__global__ __launch_bounds__(64) void k_tree_rm_find(const LevelView* views, TreeRmFind F) {
-    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (j >= F.k) return;
-    const LevelView L0 = views[0];
-    const uint64_t want = F.idx[j];
-    size_t lo = 0, hi = L0.n;
-    while (lo < hi) {
-        const size_t mid = (lo + hi) >> 1;
-        if (L0.idx[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= L0.n || L0.idx[lo] != want) { atomicOr(F.missing, 1u); return; }
-    const size_t stride = (size_t)F.height + 1;
-    uint32_t* pos = F.pos + j * stride;
-    uint8_t* hp = F.has_pad + j * stride;
-    size_t p = lo;
-    for (int t = 0; t < F.height; t++) { pos[t] = (uint32_t)p; hp[t] = views[t].has_pad[p]; p = views[t].parent[p]; }
-    pos[F.height] = (uint32_t)p;
-    hp[F.height] = 0;
-}
-// R2: one lane per chain top; level[i] / pos[i] = level and (new) position of the surviving sibling S.
-__global__ __launch_bounds__(64) void k_tree_rm_pad(TableView tbl, const LevelView* views, size_t n, const uint8_t* level, const uint32_t* pos,
-                                                    const uint32_t* pad_seed) {
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const int t = level[i];
-    const size_t s = pos[i];
-    const LevelView L = views[t];
-    uint32_t seed[8], wide[16], rB[8], cB[8], hB[8];
-    for (int k = 0; k < 8; k++) seed[k] = pad_seed[k];
-    seed_wide(wide, seed, 1u, (uint64_t)t, L.idx[s] ^ 1ull);
-    sc rm;
-    sc_from_wide(rm, wide);
-    sc_from_mont(rB, rm);
-    ge_p3 pB;
-    ge_identity(pB);
-    tbl_fixed_mul_add(pB, tbl, tbl.row_Bb(0), rB);
-    ge_compress(cB, pB);
-    node_hash32(tbl.digest, hB, cB);
-    st8(L.padC + s * 8, cB);
-    st8(L.padH + s * 8, hB);
-    st8(L.padr + s * 8, rB);
-    L.has_pad[s] = 1;
-}
-// R3, one level: pc[2 i] = position of a touched survivor in nxt, pc[2 i + 1] = position of one of its surviving children in cur
-// (new layout).  The other child is the padding record of that child or its real neighbour, as k_tree_merge pairs them.
-__global__ __launch_bounds__(64) void k_tree_rm_merge(int digest, LevelView cur, LevelView nxt, size_t n, const uint32_t* pc) {
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const size_t p = pc[2 * i], c = pc[2 * i + 1];
-    const bool left = (cur.idx[c] & 1ull) == 0;
-    uint32_t cA[8], hA[8], rA[8], cB[8], hB[8], rB[8];
-    const uint64_t vA = cur.v[c];
-    uint64_t vB = 0;
-    ld8(cA, cur.C + c * 8); ld8(hA, cur.H + c * 8); ld8(rA, cur.r + c * 8);
-    if (cur.has_pad[c]) { ld8(cB, cur.padC + c * 8); ld8(hB, cur.padH + c * 8); ld8(rB, cur.padr + c * 8); }
-    else {
-        const size_t s = left ? c + 1 : c - 1;
-        ld8(cB, cur.C + s * 8); ld8(hB, cur.H + s * 8); ld8(rB, cur.r + s * 8);
-        vB = cur.v[s];
-    }
-    ge_p3 pA, pB, pp;
-    (void)ge_decompress(pA, cA);                   // the tree's own encodings: always decode
-    (void)ge_decompress(pB, cB);
-    ge_add(pp, pA, pB);
-    sc ma, mb, ms;
-    sc_to_mont(ma, rA);
-    sc_to_mont(mb, rB);
-    sc_add(ms, ma, mb);
-    uint32_t rp[8], cp[8], hp[8];
-    sc_from_mont(rp, ms);
-    ge_compress(cp, pp);
-    if (left) node_hash128(digest, hp, cA, cB, hA, hB);
-    else node_hash128(digest, hp, cB, cA, hB, hA);
-    nxt.v[p] = vA + vB;                            // u64 wrap == release-mode Rust (node.rs:72)
-    st8(nxt.r + p * 8, rp);
-    st8(nxt.C + p * 8, cp);
-    st8(nxt.H + p * 8, hp);
-}
 
 // ------------------------------------------------------------------------------------- small trees, by phases
 // k_tree_merge makes a level in one pass, which is right for millions of nodes (one trip through HBM) and wrong for a tree of a
@@ -1055,20 +985,10 @@ __global__ __launch_bounds__(64) void k_tree_padding_all(TableView tbl, const Le
     const size_t i = t - lvl_off[level];
     const LevelView cur = views[level];
     if (i >= cnt[level] || !cur.has_pad[i]) return;
-    uint32_t seed[8], wide[16], rB[8], cB[8], hB[8];
-    for (int k = 0; k < 8; k++) seed[k] = pad_seed[k];
-    seed_wide(wide, seed, 1u, (uint64_t)level, cur.idx[i] ^ 1ull);  // Paddable::padding with the positional blinding (k_tree_merge)
-    sc rm;
-    sc_from_wide(rm, wide);
-    sc_from_mont(rB, rm);
+    uint32_t rB[8], cB[8], hB[8];
     ge_p3 pB;
-    ge_identity(pB);
-    tbl_fixed_mul_add(pB, tbl, tbl.row_Bb(0), rB);
-    ge_compress(cB, pB);
-    node_hash32(tbl.digest, hB, cB);
-    st8(cur.padC + i * 8, cB);
-    st8(cur.padH + i * 8, hB);
-    st8(cur.padr + i * 8, rB);
+    padding_node(pB, rB, cB, hB, tbl, pad_seed, (uint64_t)level, cur.idx[i] ^ 1ull);
+    store_pad_record(cur, i, cB, hB, rB);
     st_p3(extpad + t * 40, pB);
 }
 __global__ __launch_bounds__(64) void k_tree_sum_level(LevelView cur, LevelView nxt, int level, const uint32_t* cnt, const int32_t* ext_cur,
@@ -1091,11 +1011,7 @@ __global__ __launch_bounds__(64) void k_tree_sum_level(LevelView cur, LevelView 
         ld8(rB, cur.padr + i * 8);
         ld_p3(pB, extpad_cur + i * 40);
     }
-    sc ma, mb, ms;                                                   // r = (r_L + r_R) mod l  (node.rs:75)
-    sc_to_mont(ma, rA);
-    sc_to_mont(mb, rB);
-    sc_add(ms, ma, mb);
-    sc_from_mont(rp, ms);
+    sc_add_words(rp, rA, rB);
     ge_add(pp, pA, pB);
     nxt.v[q] = cur.v[i] + vB;                                        // u64 wrap == release-mode Rust (node.rs:72)
     st8(nxt.r + (size_t)q * 8, rp);
@@ -1123,10 +1039,8 @@ __global__ __launch_bounds__(64) void k_tree_hash_level(int digest, LevelView cu
     uint32_t cA[8], hA[8], cB[8], hB[8], hp[8];
     ld8(cA, cur.C + i * 8);
     ld8(hA, cur.H + i * 8);
-    if (pair) { ld8(cB, cur.C + (i + 1) * 8); ld8(hB, cur.H + (i + 1) * 8); }
-    else { ld8(cB, cur.padC + i * 8); ld8(hB, cur.padH + i * 8); }
-    if (pair || (cur.idx[i] & 1ull) == 0) node_hash128(digest, hp, cA, cB, hA, hB);       // Mergeable::merge (node.rs:64-80)
-    else node_hash128(digest, hp, cB, cA, hB, hA);
+    load_other_child(cB, hB, nullptr, nullptr, cur, i, true);        // (this lane is the left node of a pair, or has a padding sibling)
+    parent_hash(digest, hp, pair || (cur.idx[i] & 1ull) == 0, cA, cB, hA, hB);
     st8(nxt.H + (size_t)q * 8, hp);
 }
 
@@ -1150,11 +1064,7 @@ __global__ void k_tree_find_leaves(size_t b, const uint64_t* want, size_t n, con
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= b) return;
     uint64_t w = want[t];
-    size_t lo = 0, hi = n;
-    while (lo < hi) {
-        size_t mid = (lo + hi) >> 1;
-        if (idx[mid] < w) lo = mid + 1; else hi = mid;
-    }
+    size_t lo = lower_bound_u64(idx, n, w);
     if (lo < n && idx[lo] == w) pos[t] = (uint32_t)lo;
     else { pos[t] = 0xffffffffu; atomicOr(missing, 1u); }
 }
@@ -1170,18 +1080,8 @@ __global__ __launch_bounds__(64) void k_tree_path_walk(size_t b, uint32_t* pos, 
         // sibling order of a proof (dapol_wire_config.siblings_leaf_first): root side first (slot 0 = the root's child) or leaf first
         size_t slot = t * (size_t)(height + n_upper) + (size_t)(leaf_first ? level : n_upper + height - 1 - level);
         uint32_t c[8], h[8], r[8];
-        uint64_t v = 0;
-        if (lv.has_pad[p]) {
-            ld8(c, lv.padC + (size_t)p * 8);
-            ld8(h, lv.padH + (size_t)p * 8);
-            ld8(r, lv.padr + (size_t)p * 8);
-        } else {
-            size_t s = (lv.idx[p] & 1ull) ? (size_t)p - 1 : (size_t)p + 1;
-            ld8(c, lv.C + s * 8);
-            ld8(h, lv.H + s * 8);
-            ld8(r, lv.r + s * 8);
-            v = lv.v[s];
-        }
+        uint64_t v;
+        load_other_child(c, h, r, &v, lv, p);
         if (out.C) st8(out.C + slot * 8, c);
         if (out.H) st8(out.H + slot * 8, h);
         if (out.v) out.v[slot] = v;
@@ -1291,8 +1191,7 @@ __global__ void k_merge_records(int dg, size_t n, const uint32_t* CL, const uint
     if (v) {
         uint32_t ra[8], rb[8], rp[8];
         ld8(ra, rL + i * 8); ld8(rb, rR + i * 8);
-        sc ma, mb, ms;
-        sc_to_mont(ma, ra); sc_to_mont(mb, rb); sc_add(ms, ma, mb); sc_from_mont(rp, ms);
+        sc_add_words(rp, ra, rb);
         st8(r + i * 8, rp);
         v[i] = vL[i] + vR[i];
     }

@@ -67,7 +67,7 @@ static size_t padding_positions(int height, size_t n, const uint64_t* leaf_idx, 
     return k;
 }
 
-// In-place insert of k new leaves (sorted, distinct, no two chains sharing a node), from what k_tree_ins_plan returns: m[j] = length of
+// In-place insert of k new leaves (sorted, distinct, no two chains sharing a node), from what k_tree_ins_plan<true> returns: m[j] = length of
 // leaf j's chain of new nodes, inspos[j][t] = old-layout lower bound of chain node t < m[j], inspos[j][m[j]] = position of the first
 // ancestor that exists.  Rows have H + 1 entries.
 struct InsertPlan {
@@ -98,7 +98,7 @@ static InsertPlan plan_insert(size_t k, int H, const uint32_t* m, const uint32_t
     return P;
 }
 
-// In-place removal of k leaves (si sorted, distinct), from what k_tree_rm_find returns: pos[j][t] / has_pad[j][t] = position and
+// In-place removal of k leaves (si sorted, distinct), from what k_tree_find_paths returns: pos[j][t] / has_pad[j][t] = position and
 // has_pad flag of leaf j's ancestor at level t, old layout; rows have H + 1 entries.  The touched nodes of level t are the distinct
 // pos[j][t] in order (the leaves are sorted, so are their ancestors' positions).  A node dies iff all its real children die; a dead
 // node whose parent survives is a chain top, and its surviving sibling S takes a padding node.
@@ -167,7 +167,7 @@ static RemovePlan plan_remove(int H, size_t k, const uint64_t* si, const uint32_
 }
 
 // In-place insert of k new leaves in general -- chains may share nodes (a sibling pair, a whole new subtree) -- from what
-// k_tree_ins_plan_all returns: x = the indexes, sorted and distinct; m[j] = length of leaf j's chain of new nodes; pos_all[j][t] = the
+// k_tree_ins_plan<false> returns: x = the indexes, sorted and distinct; m[j] = length of leaf j's chain of new nodes; pos_all[j][t] = the
 // old-layout lower bound of x[j] >> t at every level t <= H (for t >= m[j] the ancestor's exact position).  Rows have H + 1 entries.
 //   The FRESH nodes of level t are the distinct x[j] >> t in ascending order: the new ones (t < m[j]) and, above them, the existing
 // ancestors the call has to merge again.  A fresh node's position in the new layout is its lower bound plus the number of NEW nodes

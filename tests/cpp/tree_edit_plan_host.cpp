@@ -1,7 +1,7 @@
 // Host-only build of the tree edit planning (dapol_amd/csrc/tree_edit_plan.inc): reads one case per line from stdin and prints the
 // plan of each as one line of JSON.  Build + run: tests/test_tree_edit_plan_cpu.py.  Cases (numbers in decimal, S1 = H + 1):
-//   remove H k si[k] pos[k * S1] has_pad[k * S1]       what k_tree_rm_find returns        -> RemovePlan
-//   insert H k m[k] inspos[k * S1]                      what k_tree_ins_plan returns       -> InsertPlan
+//   remove H k si[k] pos[k * S1] has_pad[k * S1]       what k_tree_find_paths returns     -> RemovePlan
+//   insert H k m[k] inspos[k * S1]                      what k_tree_ins_plan<true> returns -> InsertPlan
 //   merge n0 idx[n0] v[n0] k idx[k] removing [v[k]]     a leaf set and k edits             -> merge_leaf_edits
 //   slw k idx[k]                                                                           -> sorted_last_wins
 //   pad H n idx[n]                                                                         -> padding_positions

@@ -1,6 +1,6 @@
 // Host-only build of the general insert's planning (dapol_amd/csrc/tree_edit_plan.inc, plan_insert_general): reads one case per line
 // from stdin and prints its plan as one line of JSON.  Build + run: tests/test_tree_insert_plan_cpu.py.  A case (numbers in decimal,
-// S1 = H + 1) is what k_tree_ins_plan_all returns for a sorted batch:
+// S1 = H + 1) is what k_tree_ins_plan<false> returns for a sorted batch:
 //   H k x[k] m[k] pos_all[k * S1]
 #include <cstdint>
 #include <cstdio>

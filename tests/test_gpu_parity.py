@@ -1940,8 +1940,9 @@ def test_high_half_rows_do_not_change_bytes(hip_lib, ref):
 @pytest.mark.parametrize("height,n", [(1, 1), (1, 2), (3, 8), (5, 1), (9, 300), (13, 8192), (16, 1024), (20, 5000), (32, 1500), (64, 700), (14, 8193)])
 def test_phased_and_levelwise_tree_builds_agree(gpu_ctx, hip_lib, height, n):
     """Trees of at most 8,192 leaves are built by phases (structure in one block, all padding nodes at once, sums and hashes level by
-    level); larger ones level by level in one merge kernel per level.  Both must leave the same tree: root, node counts and every
-    Merkle path with its secrets -- full trees, a single leaf, sibling pairs, 64-bit indexes, the switch-over sizes."""
+    level); larger ones level by level in one merge kernel per level, which makes its padding children itself (seed mode of the fused
+    kernel) when DAPOL_TREE_SPLIT=0.  All three must leave the same tree: root, node counts and every Merkle path with its secrets --
+    full trees, a single leaf, sibling pairs, 64-bit indexes, the switch-over sizes."""
     import os
     rng = np.random.default_rng(1000 * height + n)
     if n == 1 << height:
@@ -1957,7 +1958,7 @@ def test_phased_and_levelwise_tree_builds_agree(gpu_ctx, hip_lib, height, n):
             v, r = v[:len(idx)], r[:len(idx)]
     pick = idx if len(idx) <= 64 else np.sort(np.unique(idx[rng.integers(0, len(idx), size=64)]))
     got = []
-    for env in ({}, {"DAPOL_TREE_LEVELWISE": "1"}):
+    for env in ({}, {"DAPOL_TREE_LEVELWISE": "1"}, {"DAPOL_TREE_LEVELWISE": "1", "DAPOL_TREE_SPLIT": "0"}):
         os.environ.update(env)
         try:
             tr = hip_lib.Tree(gpu_ctx, height, idx, v, r, SEED)
@@ -1968,4 +1969,4 @@ def test_phased_and_levelwise_tree_builds_agree(gpu_ctx, hip_lib, height, n):
             for k in env:
                 os.environ.pop(k, None)
     for part in range(4):
-        assert got[0][part] == got[1][part], part
+        assert got[0][part] == got[1][part] == got[2][part], part

@@ -1,7 +1,7 @@
 """The host arithmetic of the tree's edit paths (dapol_amd/csrc/tree_edit_plan.inc: the plans of the in-place insert and remove, the
 merge of a rebuild, last-wins de-duplication, padding positions) against a SET MODEL of the tree written here: level t of the tree over
 leaves X is sorted({x >> t}), a node's position is its rank in its level, and has_pad means the sibling is absent.  The inputs of a plan
-(what k_tree_rm_find / k_tree_ins_plan return) come from the model of the old leaf set, the plan is checked against the model of the
+(what k_tree_find_paths / k_tree_ins_plan return) come from the model of the old leaf set, the plan is checked against the model of the
 new one.  Nothing is recorded.  tests/cpp/tree_edit_plan_host.cpp is a host-only build of the planning, run under ASan + UBSan."""
 import bisect
 import functools

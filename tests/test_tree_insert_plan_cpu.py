@@ -1,6 +1,6 @@
 """plan_insert_general (dapol_amd/csrc/tree_edit_plan.inc), the host arithmetic of dapol_tree_insert's general in-place path, against a
 SET MODEL of the tree written here: level t of the tree over leaves X is sorted({x >> t}), a node's position is its rank in its level,
-and has_pad means the sibling is absent.  The plan's inputs (what k_tree_ins_plan_all returns) come from the model of the old leaf
+and has_pad means the sibling is absent.  The plan's inputs (what k_tree_ins_plan<false> returns) come from the model of the old leaf
 set; every output is checked against the model of the new one.  Nothing is recorded.  tests/cpp/tree_insert_plan_host.cpp is a
 host-only build of the planning, run under ASan + UBSan."""
 import bisect
@@ -63,7 +63,7 @@ def draw_leaves(rng, H, n):
 
 
 def plan_line(H, X, N):
-    """What k_tree_ins_plan_all returns: m = the first level at which the leaf's ancestor exists, and the lower bound of x >> t in the
+    """What k_tree_ins_plan<false> returns: m = the first level at which the leaf's ancestor exists, and the lower bound of x >> t in the
     OLD level t for every t."""
     old = levels_of(X, H)
     xs = sorted(N)
