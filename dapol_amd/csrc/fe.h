@@ -9,13 +9,24 @@
 // limbs first and re-enter through 9 more MADs by 1216: 90 MADs + 17 carries, ~8 % fewer issue cycles per product
 // (profiles/r02_fe29_ab.txt), and a point is 36 registers instead of 40.  fe_sq: 45 + 9 MADs.
 //
-// Bounds (floor carries, so "reduced" limbs are non-negative: limbs 0..7 in [0, 2^29 + 2^17), limb 8 in [0, 2^23]):
-//   TIGHT  = |limb| <= 2^29 + 2^17  (a reduced value, its negation, or the DIFFERENCE of two reduced values);
-//   LOOSE  = up to 3x a reduced value in magnitude (2Z - C, B + A, ...).
-//   fe_mul(h, f, g): f may be LOOSE, g must be TIGHT: a column is at most 9 products of 3*2^29 * 2^29 = 27 * 2^58 < 2^63.
-//   fe_sq(h, f):     f must be TIGHT (the doubled limbs 2 f_i must fit int32; columns <= 9 * 2^59).
-//   Outputs of fe_mul / fe_sq / fe_carry are reduced.  A SUM of two reduced values is loose: carry it before it is squared
-//   or used as g.
+// Bounds, with T = 2^29 + 2^17:
+//   REDUCED = limbs 0, 2..7 in [0, 2^29), limb 8 in [0, 2^23), limb 1 in [-e, 2^29 + e) -- what fe_mul / fe_sq / fe_carry
+//             return.  Limb 1 is NOT non-negative: the carries are floor carries, but the last one (what lies above bit 255,
+//             times 19, through limb 0 into limb 1) is added to limb 1 after its own 29 bits were cut, and it has the sign of
+//             the top column.  From the input bounds (column 8 of f g is at most 9 products of 3 T^2, plus the carry of column 7
+//             and the wrapped high half of column 16; t = (c8 >> 23) * 19 + 29 bits; limb 1 receives t >> 29):
+//               fe_mul, f loose, g tight:  e = 32849   (27 T^2 * 19 / 2^52, plus the carry)
+//               fe_sq, f tight:            limb 1 in [-9733, 2^29 + 10950)   (f_4^2 >= 0: eight products can be negative, nine positive)
+//               fe_carry:                  limb 1 in [-1, 2^29]
+//             tests/limb_vectors.py derives these numbers by interval arithmetic over the columns, tests/test_limb_bounds_cpu.py
+//             and tests/test_gpu_device_arith.py assert them on operands that go to -29191 and 2^29 + 29132.
+//   TIGHT   = |limb| <= T  (a reduced value, its negation, or the DIFFERENCE of two reduced values: limb 1 of a difference
+//             is at most 2^29 + 2 * 32849 = T - 65375 in magnitude, the other limbs stay below 2^29);
+//   LOOSE   = |limb| <= 3 T: up to 3x a reduced value in magnitude (2Z - C, B + A, ...).
+//   fe_mul(h, f, g): f may be LOOSE, g must be TIGHT: a column is at most 9 products of 3 T * T = 27 T^2 < 0.85 * 2^63
+//                    with its carry and wrapped high columns.
+//   fe_sq(h, f):     f must be TIGHT (the doubled limbs 2 f_i must fit int32; columns <= 9 T^2).
+//   A SUM of two reduced values is loose: carry it before it is squared or used as g.
 #pragma once
 #include <stdint.h>
 
@@ -423,7 +434,10 @@ DAPOL_HD void fe_sq(fe& h, const fe& f) {
 }
 #undef M64
 
-// Weak carry of a LOOSE value (|limb| < 2^31 / 20) back to reduced form, all in 32-bit ops.
+// Weak carry of a LOOSE value back to reduced form, all in 32-bit ops.  Nothing overflows for any |limb| < 2^31 - 4 (a limb
+// takes at most +-4 from the one below; the top contributes 19 * (limb 8 >> 23), at most 19 * 256, to 29 bits), so the loose
+// sums ge.h hands it (G = D + C, 3 T) are well inside.  Limb 1 of the result lies in [-1, 2^29]: it is cut to 29 bits before
+// the wrapped top reaches it through limb 0.
 DAPOL_HD void fe_carry(fe& h, const fe& f) {
     int32_t h0 = f.v[0], h1 = f.v[1], h2 = f.v[2], h3 = f.v[3], h4 = f.v[4], h5 = f.v[5], h6 = f.v[6], h7 = f.v[7], h8 = f.v[8];
     h1 += h0 >> 29; h0 &= FE_M29;
@@ -566,8 +580,9 @@ DAPOL_HD bool fe_equal(const fe& f, const fe& g) {
     fe_sub(d, f, g);
     return fe_iszero(d);
 }
-// |f| as a REDUCED value (non-negative limbs): a bare negation would leave negative limbs, and a later Y - X with
-// such an X is no longer tight (this bit ge_add on decompressed points before the carry was added).
+// |f| as a REDUCED value (f reduced): a bare negation would leave every limb negative, and a later Y - X with such an X
+// is a SUM of two reduced magnitudes, no longer tight (this bit ge_add on decompressed points before the carry was added).
+// Reduced is enough for that: limb 1 may be as low as -32849 (f itself) or -1 (the carried negation), see the bounds above.
 DAPOL_HD void fe_abs(fe& h, const fe& f) {
     bool n = fe_isnegative(f);
     fe m;

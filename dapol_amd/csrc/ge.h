@@ -8,7 +8,10 @@
 
 namespace dapol {
 
-struct ge_p3 {  // extended coordinates, x = X/Z, y = Y/Z, T = XY/Z; all four REDUCED (non-negative limbs)
+// Extended coordinates, x = X/Z, y = Y/Z, T = XY/Z; all four REDUCED in the sense of fe.h: limb 1 may leave [0, 2^29) by up to
+// 32849 either way (it is negative for some products), every other limb is non-negative.  The annotations below hold for that
+// range: a difference of two reduced values is tight with 2^16 to spare, a sum of two is loose(2), 2Z -+ C is loose(3).
+struct ge_p3 {
     fe X, Y, Z, T;
 };
 struct ge_niels {  // affine precomputed point: (y+x, y-x, 2dxy), reduced

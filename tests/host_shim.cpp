@@ -5,6 +5,7 @@
 #include "../dapol_amd/csrc/ge.h"
 #include "../dapol_amd/csrc/hash.h"
 #include "../dapol_amd/csrc/sc.h"
+#include "arith_cases.h"
 using namespace dapol;
 
 static void ld(uint32_t* w, const uint8_t* b, int n) { memcpy(w, b, 4 * n); }
@@ -244,6 +245,45 @@ int t_verify_path(int height, uint64_t idx, const uint8_t* leafC, const uint8_t*
     }
     for (int i = 0; i < 8; i++) good &= (c[i] == rc[i]) & (h[i] == rh[i]);
     return good;
+}
+// Raw-limb entry points: n cases of tests/arith_cases.h each, the same cases tests/dev_shim.hip runs one per lane on the GPU.
+// f, g, out_limbs: [n][9] int32; out_words: [n][8]; flags: [n].
+void t_fe_cases(int op, int n, const int32_t* f, const int32_t* g, int32_t* out_limbs, uint32_t* out_words, int32_t* flags) {
+    for (int i = 0; i < n; i++) flags[i] = dapol_test::fe_case(op, f + 9 * i, g + 9 * i, out_limbs + 9 * i, out_words + 8 * i);
+}
+// p, q, out_limbs: [n][36] int32; neg: [n]; out_words: [n][8]
+void t_ge_cases(int op, int n, const int32_t* p, const int32_t* q, const int32_t* neg, int32_t* out_limbs, uint32_t* out_words) {
+    for (int i = 0; i < n; i++) dapol_test::ge_case(op, p + 36 * i, q + 36 * i, neg[i], out_limbs + 36 * i, out_words + 8 * i);
+}
+void t_ge_decompress_cases(int n, const uint32_t* in, int32_t* ok, int32_t* out_limbs, uint32_t* out_words) {
+    for (int i = 0; i < n; i++) ok[i] = dapol_test::ge_decompress_case(in + 8 * i, out_limbs + 36 * i, out_words + 8 * i);
+}
+void t_ge_uniform_cases(int n, const uint32_t* in, int32_t* out_limbs, uint32_t* out_words) {
+    for (int i = 0; i < n; i++) dapol_test::ge_uniform_case(in + 16 * i, out_limbs + 36 * i, out_words + 8 * i);
+}
+void t_sc_cases(int op, int n, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+    for (int i = 0; i < n; i++) dapol_test::sc_case(op, a + 8 * i, b + 8 * i, out + 8 * i);
+}
+void t_sc_wide_cases(int n, const uint32_t* w, uint32_t* out) {
+    for (int i = 0; i < n; i++) dapol_test::sc_wide_case(w + 16 * i, out + 8 * i);
+}
+// wn: [n][2] = (W, NW); digits: [n][RECODE_MAX_NW]
+void t_sc_recode_cases(int n, const int32_t* wn, const uint32_t* x, int32_t* digits) {
+    for (int i = 0; i < n; i++) dapol_test::sc_recode_case(wn[2 * i], wn[2 * i + 1], x + 8 * i, digits + dapol_test::RECODE_MAX_NW * i);
+}
+// The transcript dev_shim.hip replays per wavefront, in the one-lane Strobe: out [ncase][2][32] and pos [ncase][2] like the
+// device's, of which only holder 1 (the one-lane Strobe) is filled here.
+void t_strobe_cases(int ncase, const int32_t* kn, const char* filler, int filler_len, const uint32_t* words, const uint32_t* words_rev,
+                    int nwords_max, uint32_t* out, uint32_t* pos) {
+    (void)filler_len; (void)nwords_max;
+    for (int i = 0; i < ncase; i++) {
+        Strobe s;
+        pos[2 * i + 1] = dapol_test::strobe_replay(s, filler, kn[2 * i], words, words_rev, kn[2 * i + 1], out + 64 * i + 32,
+                                                   [](Strobe& t, const uint32_t* w, int n) {
+                                                       for (int j = 0; j < n; j++)
+                                                           for (int b = 0; b < 4; b++) strobe_absorb_byte(t, (uint8_t)(w[j] >> (8 * b)));
+                                                   });
+    }
 }
 // SHAKE256 / SHA3-512 through the generic sponge
 void t_sponge(int rate, int domain, const uint8_t* in, int n, uint8_t* out, int outlen) {
