@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("DAPOL_HIP_LIB", os.path.join(_HERE, "libdapol_hip.so"
 POLICY_PADDING, POLICY_SPLITTING = 0, 1
 PROFILE_BENCH, PROFILE_HOST = 0, 1          # dapol_options.profile: memory defaults tuned for the bench / for an embedder that shares the GPU
 DIGEST_BLAKE3, DIGEST_BLAKE2S, DIGEST_BLAKE2B = 0, 1, 2      # Blake2b: 64-byte node hashes (every H array is then (.., 64))
+DIGEST_SHA256, DIGEST_SHA3_256 = 4, 5                        # sha2::Sha256, sha3::Sha3_256: 32 bytes, every path of a BLAKE3 context (3 is reserved)
 
 
 class DapolError(RuntimeError):
@@ -314,7 +315,7 @@ class Context:
         return C[:n], H[:n]
 
     def __init__(self, device=0, max_parties=32, digest=DIGEST_BLAKE3, options=None):
-        """digest: the node hash D of Dapol<D, R> (DIGEST_BLAKE3 or DIGEST_BLAKE2S); options: an Options (dapol_options)."""
+        """digest: the node hash D of Dapol<D, R> (DIGEST_BLAKE3, DIGEST_BLAKE2S, DIGEST_BLAKE2B, DIGEST_SHA256 or DIGEST_SHA3_256); options: an Options (dapol_options)."""
         self.h = _P()
         if options is None:
             _chk(lib().dapol_ctx_create(device, max_parties, digest, ctypes.byref(self.h)))

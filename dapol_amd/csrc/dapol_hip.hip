@@ -101,6 +101,24 @@ struct DevBuf {
     }
 };
 
+// Launches of the kernels that hash nodes.  They are templates over DX (hash.h: "SHA-256 and SHA3-256"); K names the instantiation
+// with DX in it, in parentheses -- (k_tree_merge<1, DX>) -- and DX is DG_SHA256 / DG_SHA3_256 on a context of that digest and
+// DG_RUNTIME on every other one.  The rest is hipLaunchKernelGGL's argument list.
+#define DX_UNPAREN(...) __VA_ARGS__
+#define LAUNCH_DX_AS(V, K, ...)                                              \
+    {                                                                        \
+        constexpr int DX = V;                                                \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(DX_UNPAREN K), __VA_ARGS__);      \
+    }
+#define LAUNCH_DX(dg, K, ...)                                                \
+    do {                                                                     \
+        switch (dg) {                                                        \
+            case DG_SHA256: LAUNCH_DX_AS(DG_SHA256, K, __VA_ARGS__) break;   \
+            case DG_SHA3_256: LAUNCH_DX_AS(DG_SHA3_256, K, __VA_ARGS__) break; \
+            default: LAUNCH_DX_AS(DG_RUNTIME, K, __VA_ARGS__)                \
+        }                                                                    \
+    } while (0)
+
 static inline unsigned nblk(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -137,7 +155,7 @@ struct dapol_ctx {
                                      // drained, which would serialise the lanes; into this it is queued like a kernel
 };
 
-// Width of the context's node hash D: 8 words (BLAKE3, Blake2s) or 16 (Blake2b).  Every H buffer of the C ABI holds this many
+// Width of the context's node hash D: 8 words (BLAKE3, Blake2s, SHA-256, SHA3-256) or 16 (Blake2b).  Every H buffer of the C ABI holds this many
 // bytes per node (dapol_ctx_digest_bytes).
 static inline int ctx_hw(const dapol_ctx* c) { return dg_hash_words(c->tv.digest); }
 static inline size_t ctx_hash_bytes(const dapol_ctx* c) { return (size_t)ctx_hw(c) * 4; }
@@ -299,8 +317,9 @@ int32_t dapol_ctx_create_opts(int32_t device, int32_t max_parties, int32_t diges
     if (!out) return fail(DAPOL_ERR_INVALID_ARGUMENT, "out is null");
     *out = nullptr;
     if (!options_ok(options)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad dapol_options (struct_size, or a field out of range)");
-    if (digest_id != DAPOL_DIGEST_BLAKE3 && digest_id != DAPOL_DIGEST_BLAKE2S && digest_id != DAPOL_DIGEST_BLAKE2B)
-        return fail(DAPOL_ERR_INVALID_DIGEST_SIZE, "node digest must be BLAKE3, Blake2s-256 or Blake2b-512");
+    if (digest_id != DAPOL_DIGEST_BLAKE3 && digest_id != DAPOL_DIGEST_BLAKE2S && digest_id != DAPOL_DIGEST_BLAKE2B && digest_id != DAPOL_DIGEST_SHA256 &&
+        digest_id != DAPOL_DIGEST_SHA3_256)
+        return fail(DAPOL_ERR_INVALID_DIGEST_SIZE, "node digest must be BLAKE3, Blake2s-256, Blake2b-512, SHA-256 or SHA3-256");
     if (max_parties < 1 || max_parties > 1024 || (max_parties & (max_parties - 1)))
         return fail(DAPOL_ERR_INVALID_ARGUMENT, "max_parties must be a power of two in [1, 1024]");
     int count = 0;
@@ -438,7 +457,7 @@ int32_t dapol_commit_hash_batch(dapol_ctx* ctx, size_t n, const uint64_t* v, con
     HIPCHK(dv.alloc(n)); HIPCHK(dr.alloc(n * 8)); HIPCHK(dC.alloc(n * 8)); HIPCHK(dH.alloc(n * 8));
     HIPCHK(hipMemcpyAsync(dv.p, v, n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(dr.p, r32, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_commit_hash, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, ctx->tv, n, dv.p, dr.p, dC.p, dH.p, (int32_t*)nullptr);
+    LAUNCH_DX(ctx->tv.digest, (k_commit_hash<DX>), dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, ctx->tv, n, dv.p, dr.p, dC.p, dH.p, (int32_t*)nullptr);
     LAUNCH_CHECK();
     if (ctx_wide(ctx)) {                           // 64-byte digest: H = D(C) over the commitments just made
         HIPCHK(dHw.alloc(n * 16));

@@ -90,8 +90,10 @@ DAPOL_HD void seed_wide(uint32_t* out16, const uint32_t* seed8, uint32_t domain,
 // Streaming digest D over a byte string assembled from parts (leaf derivation, src/dapol/mod.rs:323-441):
 // D = BLAKE3 (any length: the chunk chaining values of inputs beyond 1024 bytes go through the caller's stack, see
 // dg_init_long) or Blake2s-256 (the reference's KAT digest, src/dapol/tests.rs:13,21).
-// Usage: dg_init / dg_init_long, dg_update* (bytes), dg_final -> eight little-endian words.
+// Usage: dg_init / dg_init_long, dg_update* (bytes), dg_final -> eight little-endian words.  Sha256Stream and Sha3Stream (below)
+// have the same interface; the leaf kernels take the state type as a template parameter.
 enum : int { DG_BLAKE3 = 0, DG_BLAKE2S = 1, DG_BLAKE2B = 2 };   // (Blake2b: node hashes only, 64 bytes -- see "wide node hashes" below)
+enum : int { DG_SHA256 = 4, DG_SHA3_256 = 5 };                  // (3 is reserved; these two have state types of their own, see "SHA-256 and SHA3-256" below)
 enum : int { B3_STACK_DEPTH = 24 };   // subtree chaining values of up to 2^24 chunks = 16 GiB (inputs here are < 2^32 + 600 bytes)
 struct Digest {
     uint32_t h[8];
@@ -234,16 +236,7 @@ DAPOL_HD void blake2b_hash192(uint32_t* out16, const uint32_t* cl, const uint32_
 // Words of one node hash of digest `kind`, and the node hash over HW-word hashes: HW = 8 -> the 32-byte digests above (by kind),
 // HW = 16 -> Blake2b-512.  Kernels that carry hashes are templates over HW; the host picks the instantiation from the context.
 DAPOL_HD int dg_hash_words(int kind) { return kind == DG_BLAKE2B ? 16 : 8; }
-template <int HW>
-DAPOL_HD void node_hash_leaf_w(int kind, uint32_t* out, const uint32_t* c8) {
-    if (HW == 16) blake2b_hash32(out, c8);
-    else node_hash32(kind, out, c8);
-}
-template <int HW>
-DAPOL_HD void node_hash_parent_w(int kind, uint32_t* out, const uint32_t* cl, const uint32_t* cr, const uint32_t* hl, const uint32_t* hr) {
-    if (HW == 16) blake2b_hash192(out, cl, cr, hl, hr);
-    else node_hash128(kind, out, cl, cr, hl, hr);
-}
+// (node_hash_leaf_w / node_hash_parent_w: below the SHA-256 and SHA3-256 section, which they dispatch to at compile time)
 
 DAPOL_HD void dg_init(Digest& d, int kind) {
     blake3_iv(d.h);                        // both digests start from the SHA-256 IV ...
@@ -409,6 +402,232 @@ DAPOL_HD uint8_t sponge_squeeze_byte(Sponge& sp) {
     uint8_t b = (uint8_t)(sp.s[sp.pos >> 3] >> (8 * (sp.pos & 7)));
     sp.pos++;
     return b;
+}
+
+// ------------------------------------------------------------------------------------- SHA-256 and SHA3-256 (digests 4 and 5)
+// D = sha2::Sha256 and D = sha3::Sha3_256: the other two hash crates of the reference's manifest (Cargo.toml:15-17,27); both pass
+// Dapol::new's only digest check, output_size() == 32 (src/dapol/mod.rs:101-103).  Every byte string stays little-endian 32-bit
+// words as everywhere in the library: SHA-256 swaps bytes once on the way in and once on the way out, Keccak's lanes are
+// little-endian already.  Pinned against hashlib (OpenSSL) by tests/test_digests_cpu.py and tests/test_digests_gpu.py.
+//
+// Neither is a run-time branch of node_hash32 / node_hash128 or a kind of Digest: a kernel that may reach Keccak's 50 state
+// registers (or a call to keccak_f1600) is allocated for them whichever digest it runs, and every kernel of the existing digests
+// has to keep its registers, scratch and occupancy (profiles/digests_kernel_resources.txt).  So the kernels that hash nodes are
+// templates over DX -- DG_RUNTIME: BLAKE3 / Blake2s / Blake2b picked by `kind` at run time, the text they always had;
+// DG_SHA256 / DG_SHA3_256: that digest, fixed at compile time -- and the leaf kernels are templates over the streaming state type.
+enum : int { DG_RUNTIME = 0 };
+
+#define SHA256_K_TABLE                                                                                                                  \
+    {0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u, \
+     0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, \
+     0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau, 0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, \
+     0x06ca6351u, 0x14292967u, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u, \
+     0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u, 0x19a4c116u, 0x1e376c08u, \
+     0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, \
+     0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u}
+// rotr32 is v_alignbit_b32; Ch and Maj are written as bit selects, Ch = e ? f : g, Maj = (a ^ b) ? c : b (gfx950: one v_bitop3_b32
+// for Ch, v_and + v_and_or for Maj)
+#define SHA256_BS0(x) (rotr32(x, 2) ^ rotr32(x, 13) ^ rotr32(x, 22))
+#define SHA256_BS1(x) (rotr32(x, 6) ^ rotr32(x, 11) ^ rotr32(x, 25))
+#define SHA256_SS0(x) (rotr32(x, 7) ^ rotr32(x, 18) ^ ((x) >> 3))
+#define SHA256_SS1(x) (rotr32(x, 17) ^ rotr32(x, 19) ^ ((x) >> 10))
+#define SHA256_CH(e, f, g) (((e) & (f)) | (~(e) & (g)))
+#define SHA256_MAJ(a, b, c) ((((a) ^ (b)) & (c)) | (~((a) ^ (b)) & (b)))
+
+// K[t] + W[t] of the block that ends a message of whole blocks (0x80, zeros, the bit length): its schedule depends on the
+// length alone, so the third compression of the 128-byte node hash takes 64 literals instead of 48 schedule steps.
+struct Sha256Kw { uint32_t v[64]; };
+constexpr uint32_t sha256_cx_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+constexpr Sha256Kw sha256_tail_kw(uint32_t bits) {
+    const uint32_t K[64] = SHA256_K_TABLE;
+    uint32_t w[64] = {};
+    w[0] = 0x80000000u;
+    w[15] = bits;
+    for (int t = 16; t < 64; t++)
+        w[t] = w[t - 16] + (sha256_cx_rotr(w[t - 15], 7) ^ sha256_cx_rotr(w[t - 15], 18) ^ (w[t - 15] >> 3)) + w[t - 7] +
+               (sha256_cx_rotr(w[t - 2], 17) ^ sha256_cx_rotr(w[t - 2], 19) ^ (w[t - 2] >> 10));
+    Sha256Kw r = {};
+    for (int t = 0; t < 64; t++) r.v[t] = K[t] + w[t];
+    return r;
+}
+
+// One compression.  FIXED = false: m = the block as sixteen big-endian words, a 16-word rolling schedule; FIXED = true: the block
+// is the tail above (m unused).  Unrolled in full: every index of w, K and kw is a literal, the eight state words never move.
+#define SHA256_STEP(a, b, c, d, e, f, g, h, t)                                                                                          \
+    {                                                                                                                                   \
+        uint32_t kw;                                                                                                                    \
+        if (FIXED) kw = kwf.v[t];                                                                                                       \
+        else {                                                                                                                          \
+            if ((t) >= 16) w[(t) & 15] += SHA256_SS1(w[((t) - 2) & 15]) + w[((t) - 7) & 15] + SHA256_SS0(w[((t) - 15) & 15]);           \
+            kw = K[t] + w[(t) & 15];                                                                                                    \
+        }                                                                                                                               \
+        const uint32_t t1 = h + SHA256_BS1(e) + SHA256_CH(e, f, g) + kw;                                                                \
+        d += t1;                                                                                                                        \
+        h = t1 + SHA256_BS0(a) + SHA256_MAJ(a, b, c);                                                                                   \
+    }
+template <bool FIXED>
+DAPOL_HD void sha256_compress_t(uint32_t* h, const uint32_t* m, const Sha256Kw& kwf) {
+    const uint32_t K[64] = SHA256_K_TABLE;
+    uint32_t w[16];
+    for (int i = 0; i < 16; i++) w[i] = FIXED ? 0u : m[i];
+    uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+#pragma unroll
+    for (int i = 0; i < 64; i += 8) {
+        SHA256_STEP(a, b, c, d, e, f, g, hh, i + 0) SHA256_STEP(hh, a, b, c, d, e, f, g, i + 1)
+        SHA256_STEP(g, hh, a, b, c, d, e, f, i + 2) SHA256_STEP(f, g, hh, a, b, c, d, e, i + 3)
+        SHA256_STEP(e, f, g, hh, a, b, c, d, i + 4) SHA256_STEP(d, e, f, g, hh, a, b, c, i + 5)
+        SHA256_STEP(c, d, e, f, g, hh, a, b, i + 6) SHA256_STEP(b, c, d, e, f, g, hh, a, i + 7)
+    }
+    h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+}
+#undef SHA256_STEP
+DAPOL_HD void sha256_compress(uint32_t* h, const uint32_t* m) {
+    const Sha256Kw none = {};
+    sha256_compress_t<false>(h, m, none);
+}
+DAPOL_HD uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
+// Leaf node hash SHA-256(C): one block = 32 data bytes, 0x80, zeros, the length 256 (the schedule's constant terms fold)
+DAPOL_HD void sha256_hash32(uint32_t* out8, const uint32_t* c8) {
+    uint32_t h[8], m[16];
+    blake3_iv(h);                                  // (BLAKE3 and Blake2s start from SHA-256's initial value)
+    for (int i = 0; i < 8; i++) m[i] = bswap32(c8[i]);
+    m[8] = 0x80000000u;
+    for (int i = 9; i < 15; i++) m[i] = 0;
+    m[15] = 256;
+    sha256_compress(h, m);
+    for (int i = 0; i < 8; i++) out8[i] = bswap32(h[i]);
+}
+// Parent node hash SHA-256(C_L || C_R || H_L || H_R): two data blocks, then the fixed tail of a 1024-bit message
+DAPOL_HD void sha256_hash128(uint32_t* out8, const uint32_t* cl, const uint32_t* cr, const uint32_t* hl, const uint32_t* hr) {
+    constexpr Sha256Kw TAIL = sha256_tail_kw(1024);
+    uint32_t h[8], m[16];
+    blake3_iv(h);
+    for (int i = 0; i < 8; i++) { m[i] = bswap32(cl[i]); m[8 + i] = bswap32(cr[i]); }
+    sha256_compress(h, m);
+    for (int i = 0; i < 8; i++) { m[i] = bswap32(hl[i]); m[8 + i] = bswap32(hr[i]); }
+    sha256_compress(h, m);
+    sha256_compress_t<true>(h, m, TAIL);
+    for (int i = 0; i < 8; i++) out8[i] = bswap32(h[i]);
+}
+// Streaming SHA-256 with the interface of Digest (dg_init / dg_update* / dg_final): buf collects little-endian words like
+// Digest's and is swapped when a block is compressed.  total counts BYTES in 64 bits: the bit length is formed from it in 64
+// bits (a 32-bit bit count would wrap at 512 MB).
+struct Sha256Stream {
+    uint32_t h[8];
+    uint32_t buf[16];
+    uint32_t buflen;      // bytes in buf (< 64 between calls)
+    uint64_t total;       // bytes compressed so far (before buf)
+    static constexpr bool overflow = false;        // (any length: nothing like BLAKE3's chunk stack)
+};
+DAPOL_HD void dg_init(Sha256Stream& d, int /*kind*/) {
+    blake3_iv(d.h);
+    for (int i = 0; i < 16; i++) d.buf[i] = 0;
+    d.buflen = 0;
+    d.total = 0;
+}
+DAPOL_HD void sha256_block(Sha256Stream& d) {
+    uint32_t m[16];
+    for (int i = 0; i < 16; i++) { m[i] = bswap32(d.buf[i]); d.buf[i] = 0; }
+    sha256_compress(d.h, m);
+    d.buflen = 0;
+    d.total += 64;
+}
+DAPOL_HD void dg_update_byte(Sha256Stream& d, uint8_t b) {
+    d.buf[d.buflen >> 2] |= (uint32_t)b << (8 * (d.buflen & 3));
+    if (++d.buflen == 64) sha256_block(d);
+}
+DAPOL_HD void dg_final(Sha256Stream& d, uint32_t* out8) {
+    const uint64_t bits = (d.total + d.buflen) * 8ull;
+    dg_update_byte(d, 0x80);
+    if (d.buflen > 56) sha256_block(d);            // no room for the length: it goes into a block of its own
+    uint32_t m[16];
+    for (int i = 0; i < 14; i++) m[i] = bswap32(d.buf[i]);
+    m[14] = (uint32_t)(bits >> 32);
+    m[15] = (uint32_t)bits;
+    sha256_compress(d.h, m);
+    for (int i = 0; i < 8; i++) out8[i] = bswap32(d.h[i]);
+}
+
+// SHA3-256: rate 136 bytes (17 lanes), domain byte 0x06, final bit 0x80 at byte 135 (the top byte of lane 16), output = the
+// first four lanes.  Both node hashes fit one block, built directly into lanes: one permutation each.
+enum : uint32_t { SHA3_256_RATE = 136 };
+DAPOL_HD void sha3_256_hash32(uint32_t* out8, const uint32_t* c8) {
+    uint64_t A[25];
+    for (int i = 0; i < 4; i++) A[i] = w64(c8, i);
+    A[4] = 0x06ull;
+    for (int i = 5; i < 25; i++) A[i] = 0;
+    A[16] = 0x80ull << 56;
+    keccak_f1600(A);
+    for (int i = 0; i < 4; i++) { out8[2 * i] = (uint32_t)A[i]; out8[2 * i + 1] = (uint32_t)(A[i] >> 32); }
+}
+DAPOL_HD void sha3_256_hash128(uint32_t* out8, const uint32_t* cl, const uint32_t* cr, const uint32_t* hl, const uint32_t* hr) {
+    uint64_t A[25];
+    for (int i = 0; i < 4; i++) { A[i] = w64(cl, i); A[4 + i] = w64(cr, i); A[8 + i] = w64(hl, i); A[12 + i] = w64(hr, i); }
+    A[16] = 0x06ull | (0x80ull << 56);
+    for (int i = 17; i < 25; i++) A[i] = 0;
+    keccak_f1600(A);
+    for (int i = 0; i < 4; i++) { out8[2 * i] = (uint32_t)A[i]; out8[2 * i + 1] = (uint32_t)(A[i] >> 32); }
+}
+// Streaming SHA3-256: the 200-byte state is the whole of it -- every byte is XORed in where it lands and the state is permuted
+// when the rate is full.  A type of its own, not a kind of Digest: Digest would grow by 136 bytes for every digest's leaf kernels.
+struct Sha3Stream {
+    uint64_t s[25];
+    uint32_t pos;         // bytes absorbed into the current block (< 136 between calls)
+    static constexpr bool overflow = false;
+};
+DAPOL_HD void dg_init(Sha3Stream& d, int /*kind*/) {
+    for (int i = 0; i < 25; i++) d.s[i] = 0;
+    d.pos = 0;
+}
+DAPOL_HD void dg_update_byte(Sha3Stream& d, uint8_t b) {
+    d.s[d.pos >> 3] ^= (uint64_t)b << (8 * (d.pos & 7));
+    if (++d.pos == SHA3_256_RATE) {
+        keccak_f1600(d.s);
+        d.pos = 0;
+    }
+}
+DAPOL_HD void dg_final(Sha3Stream& d, uint32_t* out8) {
+    d.s[d.pos >> 3] ^= 0x06ull << (8 * (d.pos & 7));
+    d.s[16] ^= 0x80ull << 56;
+    keccak_f1600(d.s);
+    for (int i = 0; i < 4; i++) { out8[2 * i] = (uint32_t)d.s[i]; out8[2 * i + 1] = (uint32_t)(d.s[i] >> 32); }
+}
+// The rest of Digest's interface for the two state types (Digest's own functions are the better match for a Digest)
+template <class D>
+DAPOL_HD void dg_init_long(D& d, int kind, uint32_t* /*stack: BLAKE3's*/) { dg_init(d, kind); }
+template <class D>
+DAPOL_HD void dg_update(D& d, const uint8_t* p, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) dg_update_byte(d, p[i]);
+}
+template <class D>
+DAPOL_HD void dg_update_words(D& d, const uint32_t* w, int nwords) {
+    for (int i = 0; i < nwords; i++)
+        for (int k = 0; k < 4; k++) dg_update_byte(d, (uint8_t)(w[i] >> (8 * k)));
+}
+
+// The node hash as the kernels call it: HW = words of a node hash (8, or 16 for Blake2b-512), DX = DG_RUNTIME (the digest is
+// `kind`, one of the three BLAKE ones) or the digest itself (DG_SHA256 / DG_SHA3_256; `kind` equals DX and is not looked at).
+template <int DX>
+DAPOL_HD void node_hash32_x(int kind, uint32_t* out8, const uint32_t* c8) {
+    if (DX == DG_SHA256) sha256_hash32(out8, c8);
+    else if (DX == DG_SHA3_256) sha3_256_hash32(out8, c8);
+    else node_hash32(kind, out8, c8);
+}
+template <int DX>
+DAPOL_HD void node_hash128_x(int kind, uint32_t* out8, const uint32_t* cl, const uint32_t* cr, const uint32_t* hl, const uint32_t* hr) {
+    if (DX == DG_SHA256) sha256_hash128(out8, cl, cr, hl, hr);
+    else if (DX == DG_SHA3_256) sha3_256_hash128(out8, cl, cr, hl, hr);
+    else node_hash128(kind, out8, cl, cr, hl, hr);
+}
+template <int HW, int DX = DG_RUNTIME>
+DAPOL_HD void node_hash_leaf_w(int kind, uint32_t* out, const uint32_t* c8) {
+    if (HW == 16) blake2b_hash32(out, c8);
+    else node_hash32_x<DX>(kind, out, c8);
+}
+template <int HW, int DX = DG_RUNTIME>
+DAPOL_HD void node_hash_parent_w(int kind, uint32_t* out, const uint32_t* cl, const uint32_t* cr, const uint32_t* hl, const uint32_t* hr) {
+    if (HW == 16) blake2b_hash192(out, cl, cr, hl, hr);
+    else node_hash128_x<DX>(kind, out, cl, cr, hl, hr);
 }
 
 // --------------------------------------------------------------------------------- STROBE-128 / Merlin 3.0.0

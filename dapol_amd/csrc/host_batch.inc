@@ -146,7 +146,7 @@ int32_t dapol_prove_batch(dapol_ctx* ctx, dapol_tree* tree, size_t k, const uint
 // MerkleProof::verify_batch with DapolProofNode::merge: arena slots [0, k) leaves, [k, k + S) siblings, then the
 // merged nodes level by level; `ops` = (left slot, right slot, destination slot).
 struct MergeOp { uint32_t left, right, dst; };
-template <int HW>
+template <int HW, int DX>
 __global__ void k_batch_merge(int dg, size_t n, const MergeOp* ops, uint32_t* C, uint32_t* Hh, uint32_t* bad) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -159,7 +159,7 @@ __global__ void k_batch_merge(int dg, size_t n, const MergeOp* ops, uint32_t* C,
     if (!ok) atomicOr(bad, 1u);
     ge_add(p, a, b);
     ge_compress(cp, p);
-    node_hash_parent_w<HW>(dg, hp, cl, cr, hl, hr);
+    node_hash_parent_w<HW, DX>(dg, hp, cl, cr, hl, hr);
     st8(C + (size_t)o.dst * 8, cp);
     sth<HW>(Hh + (size_t)o.dst * HW, hp);
 }
@@ -234,8 +234,8 @@ int32_t dapol_verify_batch(dapol_ctx* ctx, int32_t height, size_t k, const uint6
     size_t done = 0;
     for (size_t lv = 0; lv < level_ops.size(); lv++) {
         size_t n = level_ops[lv] - done;
-        if (hw == 16) hipLaunchKernelGGL(k_batch_merge<16>, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, n, dops.p + done, aC.p, aH.p, bad.p);
-        else hipLaunchKernelGGL(k_batch_merge<8>, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, n, dops.p + done, aC.p, aH.p, bad.p);
+        if (hw == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_batch_merge<16, DG_RUNTIME>), dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, n, dops.p + done, aC.p, aH.p, bad.p);
+        else LAUNCH_DX(ctx->tv.digest, (k_batch_merge<8, DX>), dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, n, dops.p + done, aC.p, aH.p, bad.p);
         LAUNCH_CHECK();
         done = level_ops[lv];
     }

@@ -181,6 +181,7 @@ int32_t dapol_comm_count(dapol_comm* c, int32_t* count) {
 }
 
 // parents of n pairs of records: out[i] = merge(in[2i], in[2i+1])  (Mergeable::merge, src/dapol/node.rs:64-80)
+template <int DX>
 __global__ void k_merge_pairs(int dg, size_t n, const uint32_t* C, const uint32_t* H, const uint64_t* v, const uint32_t* r, uint32_t* oC, uint32_t* oH,
                               uint64_t* ov, uint32_t* orr, uint32_t* bad) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -191,7 +192,7 @@ __global__ void k_merge_pairs(int dg, size_t n, const uint32_t* C, const uint32_
     if (!(ge_decompress(a, cl) & ge_decompress(b, cr))) { atomicOr(bad, 1u); return; }
     ge_add(p, a, b);
     ge_compress(cp, p);
-    node_hash128(dg, hp, cl, cr, hl, hr);
+    node_hash128_x<DX>(dg, hp, cl, cr, hl, hr);
     ld8(ra, r + 16 * i); ld8(rb, r + 16 * i + 8);
     sc ma, mb, ms;
     sc_to_mont(ma, ra); sc_to_mont(mb, rb); sc_add(ms, ma, mb); sc_from_mont(rp, ms);
@@ -232,7 +233,7 @@ static int32_t top_levels_device(dapol_ctx* ctx, int world, int rank, const uint
         if (up_H32) HIPCHK(hipMemcpyAsync(up_H32 + 32 * slot, H[cur].p + 8 * s, 32, hipMemcpyDeviceToHost, st));
         if (up_r32) HIPCHK(hipMemcpyAsync(up_r32 + 32 * slot, r[cur].p + 8 * s, 32, hipMemcpyDeviceToHost, st));
         if (up_v) HIPCHK(hipMemcpyAsync(up_v + slot, v[cur].p + s, 8, hipMemcpyDeviceToHost, st));
-        hipLaunchKernelGGL(k_merge_pairs, dim3(nblk(g / 2, 64)), dim3(64), 0, st, ctx->tv.digest, g / 2, C[cur].p, H[cur].p, v[cur].p, r[cur].p,
+        LAUNCH_DX(ctx->tv.digest, (k_merge_pairs<DX>), dim3(nblk(g / 2, 64)), dim3(64), 0, st, ctx->tv.digest, g / 2, C[cur].p, H[cur].p, v[cur].p, r[cur].p,
                            C[cur ^ 1].p, H[cur ^ 1].p, v[cur ^ 1].p, r[cur ^ 1].p, bad.p);
         LAUNCH_CHECK();
         cur ^= 1; g /= 2; pos >>= 1;
@@ -365,7 +366,7 @@ int32_t dapol_shard_top_node_records(dapol_ctx* ctx, int32_t world, const uint8_
     LAUNCH_CHECK();
     for (int t = 0; t < bits; t++) {
         const size_t g = G >> t, a = off[t], b = off[t + 1];
-        hipLaunchKernelGGL(k_merge_pairs, dim3(nblk(g / 2, 64)), dim3(64), 0, st, ctx->tv.digest, g / 2, C.p + a * 8, H.p + a * 8, vv.p + a, r.p + a * 8,
+        LAUNCH_DX(ctx->tv.digest, (k_merge_pairs<DX>), dim3(nblk(g / 2, 64)), dim3(64), 0, st, ctx->tv.digest, g / 2, C.p + a * 8, H.p + a * 8, vv.p + a, r.p + a * 8,
                            C.p + b * 8, H.p + b * 8, vv.p + b, r.p + b * 8, bad.p);
         LAUNCH_CHECK();
     }

@@ -22,6 +22,16 @@ __global__ void k_leaf_gather(size_t n, const uint32_t* ord, const uint64_t* val
     for (int i = 0; i < 8; i++) r_sorted[p * 8 + i] = blind[(size_t)e * 8 + i];
 }
 
+// Launches of the leaf kernels that hash: the instantiation over the streaming state of digest `kind`.
+#define LAUNCH_LEAF(kind, K, ...)                                                        \
+    do {                                                                                 \
+        switch (kind) {                                                                  \
+            case DG_SHA256: hipLaunchKernelGGL(K<Sha256Stream>, __VA_ARGS__); break;     \
+            case DG_SHA3_256: hipLaunchKernelGGL(K<Sha3Stream>, __VA_ARGS__); break;     \
+            default: hipLaunchKernelGGL(K<Digest>, __VA_ARGS__);                         \
+        }                                                                                \
+    } while (0)
+
 // build_leaf_nodes over n liabilities that join the leaves O (none for dapol_build_leaf_nodes): a candidate that is one of O is taken
 // before the batch starts (kernels_leaf.h, LeafOccupied); the sparsity rule of Dapol::new counts O's leaves too.
 static int32_t leaf_derive(dapol_ctx* ctx, int32_t digest_id, const uint8_t* audit_seed, size_t audit_seed_len, int32_t height, size_t n,
@@ -31,7 +41,8 @@ static int32_t leaf_derive(dapol_ctx* ctx, int32_t digest_id, const uint8_t* aud
     if (!ctx || !n || !internal_off || !external_off || !values || !leaf_idx_sorted || !v_sorted || !r32_sorted || !order_sorted ||
         (audit_seed_len && !audit_seed))
         return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    if (digest_id != DAPOL_DIGEST_BLAKE3 && digest_id != DAPOL_DIGEST_BLAKE2S) return fail(DAPOL_ERR_INVALID_DIGEST_SIZE, "digest must be BLAKE3 or Blake2s (32 bytes)");
+    if (digest_id != DAPOL_DIGEST_BLAKE3 && digest_id != DAPOL_DIGEST_BLAKE2S && digest_id != DAPOL_DIGEST_SHA256 && digest_id != DAPOL_DIGEST_SHA3_256)
+        return fail(DAPOL_ERR_INVALID_DIGEST_SIZE, "digest must be BLAKE3, Blake2s-256, SHA-256 or SHA3-256 (32 bytes)");
     if (height > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
     if (height < 1) return fail(DAPOL_ERR_INVALID_ARGUMENT, "tree height must be at least 1");
     if (height < 64 && (double)(n + O.n) * 2.0 > (double)(1ull << height)) return fail(DAPOL_ERR_SPARSITY_TOO_SMALL, "2^height < 2 * number of liabilities");
@@ -56,13 +67,13 @@ static int32_t leaf_derive(dapol_ctx* ctx, int32_t digest_id, const uint8_t* aud
     HIPCHK(hipMemcpyAsync(dvals.p, values, n * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(err.p, 0, 16, st));
     LeafArgs A{};
-    A.n = n; A.height = height; A.kind = digest_id == DAPOL_DIGEST_BLAKE2S ? DG_BLAKE2S : DG_BLAKE3;
+    A.n = n; A.height = height; A.kind = digest_id;   // (the DAPOL_DIGEST_* ids are the DG_* kinds)
     A.seed = dseed.p; A.seed_len = (uint32_t)audit_seed_len;
     A.iid = diid.p; A.iid_off = dioff.p; A.eid = deid.p; A.eid_off = deoff.p;
     A.audit_id = aid.p; A.idx_state = state.p; A.cand = cand.p; A.blind = blind.p; A.err = err.p;
     A.max_tries = LEAF_MAX_RETRIES;
     if (const char* e = test_knob("DAPOL_LEAF_MAX_TRIES")) A.max_tries = std::min((int)LEAF_MAX_RETRIES, std::max(1, atoi(e)));   // test knob (DAPOL_TEST_HOOKS=1 beside DAPOL_ENV_KNOBS)
-    hipLaunchKernelGGL(k_leaf_hash, dim3(nblk(n, 64)), dim3(64), 0, st, A); LAUNCH_CHECK();
+    LAUNCH_LEAF(A.kind, k_leaf_hash, dim3(nblk(n, 64)), dim3(64), 0, st, A); LAUNCH_CHECK();
     // duplicate internal ids
     hipLaunchKernelGGL(k_leaf_dup_keys, dim3(nblk(n, 256)), dim3(256), 0, st, n, aid.p, key.p, ord.p); LAUNCH_CHECK();
     int32_t rc = sort_pairs_u64_u32(st, key.p, key2.p, ord.p, ord2.p, n);
@@ -92,8 +103,8 @@ static int32_t leaf_derive(dapol_ctx* ctx, int32_t digest_id, const uint8_t* aud
         uint32_t hflags[2] = {1, 0};
         for (int round = 0; round < 100000 && hflags[0] && !hflags[1]; round++) {
             HIPCHK(hipMemsetAsync(tflags.p, 0, 4, st));
-            if (O.n) hipLaunchKernelGGL(k_leaf_settle_onto, dim3(nblk(n, 256)), dim3(256), 0, st, A, T, O);
-            else hipLaunchKernelGGL(k_leaf_settle, dim3(nblk(n, 256)), dim3(256), 0, st, A, T);
+            if (O.n) LAUNCH_LEAF(A.kind, k_leaf_settle_onto, dim3(nblk(n, 256)), dim3(256), 0, st, A, T, O);
+            else LAUNCH_LEAF(A.kind, k_leaf_settle, dim3(nblk(n, 256)), dim3(256), 0, st, A, T);
             LAUNCH_CHECK();
             HIPCHK(hipMemcpyAsync(hflags, tflags.p, 8, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
@@ -109,7 +120,7 @@ static int32_t leaf_derive(dapol_ctx* ctx, int32_t digest_id, const uint8_t* aud
             }
         }
         if (!resolved) {                                                        // table full (cannot happen at 4 n slots in practice): start over, one lane
-            hipLaunchKernelGGL(k_leaf_hash, dim3(nblk(n, 64)), dim3(64), 0, st, A); LAUNCH_CHECK();
+            LAUNCH_LEAF(A.kind, k_leaf_hash, dim3(nblk(n, 64)), dim3(64), 0, st, A); LAUNCH_CHECK();
             HIPCHK(hipMemsetAsync(err.p, 0, 16, st));
         }
     }
@@ -136,7 +147,7 @@ static int32_t leaf_derive(dapol_ctx* ctx, int32_t digest_id, const uint8_t* aud
         R.n = n; R.skey = key2.p; R.sord = ord2.p; R.heap = losers.p; R.heap_n = n_losers; R.evicted = evicted.p;
         R.tab_key = tab_key.p; R.tab_used = tab_used.p; R.tab_mask = (uint32_t)(tsz - 1);
         R.occ = O;
-        hipLaunchKernelGGL(k_leaf_resolve, dim3(1), dim3(64), 0, st, A, R); LAUNCH_CHECK();
+        LAUNCH_LEAF(A.kind, k_leaf_resolve, dim3(1), dim3(64), 0, st, A, R); LAUNCH_CHECK();
         HIPCHK(hipMemcpyAsync(herr, err.p, 16, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (herr[2]) {

@@ -257,10 +257,10 @@ int32_t dapol_proof_store_verify(dapol_proof_store* s, const uint8_t verify_seed
     LAUNCH_CHECK();
     const dapol_proof_store::Siblings& cur = s->set[s->cur];
     if (wide)
-        hipLaunchKernelGGL(k_verify_paths<16>, dim3(nblk(b, 64)), dim3(64), 0, st, ctx->tv.digest, b, H, s->idx.p, dLC, dLH, cur.C.p, cur.H.p, top.C, rootH,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify_paths<16, DG_RUNTIME>), dim3(nblk(b, 64)), dim3(64), 0, st, ctx->tv.digest, b, H, s->idx.p, dLC, dLH, cur.C.p, cur.H.p, top.C, rootH,
                            g_wire.siblings_leaf_first, dpath);
     else
-        hipLaunchKernelGGL(k_verify_paths<8>, dim3(nblk(b, 64)), dim3(64), 0, st, ctx->tv.digest, b, H, s->idx.p, dLC, dLH, cur.C.p, cur.H.p, top.C, rootH,
+        LAUNCH_DX(ctx->tv.digest, (k_verify_paths<8, DX>), dim3(nblk(b, 64)), dim3(64), 0, st, ctx->tv.digest, b, H, s->idx.p, dLC, dLH, cur.C.p, cur.H.p, top.C, rootH,
                            g_wire.siblings_leaf_first, dpath);
     LAUNCH_CHECK();
     HIPCHK(hipMemsetAsync(dok, 1, b, st));

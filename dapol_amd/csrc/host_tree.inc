@@ -160,13 +160,13 @@ static int32_t build_phased(dapol_ctx* ctx, dapol_tree* t, size_t n, const std::
     HIPCHK(hipEventRecord(ctx->ev_fork, st));
     HIPCHK(hipStreamWaitEvent(ctx->side[0], ctx->ev_fork, 0));
     fg.forked(0);
-    hipLaunchKernelGGL(k_commit_hash, dim3(nblk(n, 64)), dim3(64), 0, ctx->side[0], ctx->tv, n, t->leaf_v, t->leaf_r, t->levels[0].C.p, t->levels[0].H.p, ext_all);
+    LAUNCH_DX(ctx->tv.digest, (k_commit_hash<DX>), dim3(nblk(n, 64)), dim3(64), 0, ctx->side[0], ctx->tv, n, t->leaf_v, t->leaf_r, t->levels[0].C.p, t->levels[0].H.p, ext_all);
     LAUNCH_CHECK();
     HIPCHK(hipEventRecord(ctx->ev_join[0], ctx->side[0]));
     FAULT_AFTER_FORK("tree");
     hipLaunchKernelGGL(k_tree_structure_small, dim3(1), dim3(1024), 0, st, height, t->d_views.p, cnt);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_tree_padding_all, dim3(nblk(h_off[height], 64)), dim3(64), 0, st, ctx->tv, t->d_views.p, height, cnt, d_off, seed, extpad_all);
+    LAUNCH_DX(ctx->tv.digest, (k_tree_padding_all<DX>), dim3(nblk(h_off[height], 64)), dim3(64), 0, st, ctx->tv, t->d_views.p, height, cnt, d_off, seed, extpad_all);
     LAUNCH_CHECK();
     HIPCHK(hipStreamWaitEvent(st, ctx->ev_join[0], 0));
     fg.joined(0);
@@ -178,7 +178,7 @@ static int32_t build_phased(dapol_ctx* ctx, dapol_tree* t, size_t n, const std::
     hipLaunchKernelGGL(k_tree_compress_all, dim3(nblk(tot - h_off[1], 64)), dim3(64), 0, st, t->d_views.p, height, cnt, d_off, ext_all);
     LAUNCH_CHECK();
     for (int k = 0; k < height; k++) {
-        hipLaunchKernelGGL(k_tree_hash_level, dim3(nblk(bound[k], 64)), dim3(64), 0, st, ctx->tv.digest, hv[k], hv[k + 1], k, cnt);
+        LAUNCH_DX(ctx->tv.digest, (k_tree_hash_level<DX>), dim3(nblk(bound[k], 64)), dim3(64), 0, st, ctx->tv.digest, hv[k], hv[k + 1], k, cnt);
         LAUNCH_CHECK();
     }
     return DAPOL_OK;
@@ -206,7 +206,7 @@ static int32_t build_levelwise(dapol_ctx* ctx, dapol_tree* t, size_t n, const st
         tmp.flag = (uint32_t*)(b + o_flag); tmp.pos = (uint32_t*)(b + o_pos); tmp.head = (uint32_t*)(b + o_head); tmp.bsums = (uint32_t*)(b + o_bs);
         tmp.ext_a = (int32_t*)(b + o_a); tmp.ext_b = (int32_t*)(b + o_b); tmp.ext_pad = (int32_t*)(b + o_p);
     }
-    hipLaunchKernelGGL(k_commit_hash, dim3(nblk(n, 256)), dim3(256), 0, st, ctx->tv, n, t->leaf_v, t->leaf_r, t->levels[0].C.p, t->levels[0].H.p, tmp.ext_a);
+    LAUNCH_DX(ctx->tv.digest, (k_commit_hash<DX>), dim3(nblk(n, 256)), dim3(256), 0, st, ctx->tv, n, t->leaf_v, t->leaf_r, t->levels[0].C.p, t->levels[0].H.p, tmp.ext_a);
     LAUNCH_CHECK();
     int32_t* ext_cur = tmp.ext_a;
     int32_t* ext_nxt = tmp.ext_b;
@@ -222,11 +222,11 @@ static int32_t build_levelwise(dapol_ctx* ctx, dapol_tree* t, size_t n, const st
         LAUNCH_CHECK();
         LevelView nxt = t->view(k + 1, k + 1 < height ? ext_nxt : nullptr);
         if (split_pad) {
-            hipLaunchKernelGGL(k_tree_pad_level, dim3(nblk(bound[k + 1], 256)), dim3(256), 0, st, ctx->tv, cur, tmp.head, k, seed, cnt, tmp.ext_pad);
+            LAUNCH_DX(ctx->tv.digest, (k_tree_pad_level<DX>), dim3(nblk(bound[k + 1], 256)), dim3(256), 0, st, ctx->tv, cur, tmp.head, k, seed, cnt, tmp.ext_pad);
             LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_tree_merge<1>, dim3(nblk(bound[k + 1], 256)), dim3(256), 0, st, ctx->tv, cur, nxt, tmp.head, k, seed, cnt, ptape, tmp.ext_pad);
+            LAUNCH_DX(ctx->tv.digest, (k_tree_merge<1, DX>), dim3(nblk(bound[k + 1], 256)), dim3(256), 0, st, ctx->tv, cur, nxt, tmp.head, k, seed, cnt, ptape, tmp.ext_pad);
         } else
-            hipLaunchKernelGGL(k_tree_merge<0>, dim3(nblk(bound[k + 1], 256)), dim3(256), 0, st, ctx->tv, cur, nxt, tmp.head, k, seed, cnt, ptape, (const int32_t*)nullptr);
+            LAUNCH_DX(ctx->tv.digest, (k_tree_merge<0, DX>), dim3(nblk(bound[k + 1], 256)), dim3(256), 0, st, ctx->tv, cur, nxt, tmp.head, k, seed, cnt, ptape, (const int32_t*)nullptr);
         LAUNCH_CHECK();
         std::swap(ext_cur, ext_nxt);
     }
@@ -526,7 +526,7 @@ int32_t dapol_padding_nodes(dapol_ctx* ctx, const uint8_t pad_seed32[32], size_t
     HIPCHK(hipMemcpyAsync(seed.p, pad_seed32, 32, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dl.p, level, n, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(di.p, index, n * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_padding_nodes, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv, n, seed.p, dl.p, di.p, dC.p, dH.p, dr.p);
+    LAUNCH_DX(ctx->tv.digest, (k_padding_nodes<DX>), dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv, n, seed.p, dl.p, di.p, dC.p, dH.p, dr.p);
     LAUNCH_CHECK();
     DevBuf<uint32_t> dHw;
     if (ctx_wide(ctx)) {
@@ -568,9 +568,14 @@ int32_t dapol_merge_batch(dapol_ctx* ctx, size_t n, const uint8_t* CL32, const u
     }
     DevBuf<uint32_t> oC, oH;
     HIPCHK(oC.alloc(n * 8)); HIPCHK(oH.alloc(n * hw));
-    hipLaunchKernelGGL(hw == 16 ? k_merge_records<16> : k_merge_records<8>, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, n, d[0].p, d[1].p,
-                       with_secrets ? dv[0].p : nullptr, d[4].p, d[2].p, d[3].p, with_secrets ? dv[1].p : nullptr, d[5].p, oC.p, oH.p,
-                       with_secrets ? dv[2].p : nullptr, d[6].p, bad.p);
+    if (hw == 16)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge_records<16, DG_RUNTIME>), dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, n, d[0].p, d[1].p,
+                           with_secrets ? dv[0].p : nullptr, d[4].p, d[2].p, d[3].p, with_secrets ? dv[1].p : nullptr, d[5].p, oC.p, oH.p,
+                           with_secrets ? dv[2].p : nullptr, d[6].p, bad.p);
+    else
+        LAUNCH_DX(ctx->tv.digest, (k_merge_records<8, DX>), dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, n, d[0].p, d[1].p,
+                  with_secrets ? dv[0].p : nullptr, d[4].p, d[2].p, d[3].p, with_secrets ? dv[1].p : nullptr, d[5].p, oC.p, oH.p,
+                  with_secrets ? dv[2].p : nullptr, d[6].p, bad.p);
     LAUNCH_CHECK();
     uint32_t h_bad = 0;
     HIPCHK(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, st));

@@ -29,11 +29,11 @@ static int32_t rehash_paths(dapol_tree_owned* own, const TreeUpdArgs& U) {
     hipLaunchKernelGGL(k_tree_upd_nodes, dim3(nblk(k * (size_t)H, 64)), dim3(64), 0, st, own->d_views.p, U);
     LAUNCH_CHECK();
     if (k <= 1024) {
-        hipLaunchKernelGGL(k_tree_upd_hash, dim3(1), dim3((unsigned)align_up(k, 64)), 0, st, ctx->tv.digest, own->d_views.p, U, 0, H);
+        LAUNCH_DX(ctx->tv.digest, (k_tree_upd_hash<DX>), dim3(1), dim3((unsigned)align_up(k, 64)), 0, st, ctx->tv.digest, own->d_views.p, U, 0, H);
         LAUNCH_CHECK();
     } else {
         for (int lv = 0; lv < H; lv++) {
-            hipLaunchKernelGGL(k_tree_upd_hash, dim3(nblk(k, 256)), dim3(256), 0, st, ctx->tv.digest, own->d_views.p, U, lv, lv + 1);
+            LAUNCH_DX(ctx->tv.digest, (k_tree_upd_hash<DX>), dim3(nblk(k, 256)), dim3(256), 0, st, ctx->tv.digest, own->d_views.p, U, lv, lv + 1);
             LAUNCH_CHECK();
         }
     }
@@ -68,7 +68,7 @@ static int32_t tree_update_incremental(dapol_tree_owned* own, const HostLeaves& 
     if (missing) return DAPOL_OK;                            // a new index: nothing has been written; the caller inserts or rebuilds
     TreePoison poison{own, true};                            // from here on the leaves and the levels above are rewritten in place
     if (test_knob("DAPOL_TEST_FAIL_UPDATE_MIDWAY")) return fail(DAPOL_ERR_HIP, "injected failure between the leaf update and the re-merge (test knob)");
-    hipLaunchKernelGGL(k_tree_upd_leaves, dim3(nblk(k, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, U);
+    LAUNCH_DX(ctx->tv.digest, (k_tree_upd_leaves<DX>), dim3(nblk(k, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, U);
     LAUNCH_CHECK();
     if (H >= 1) RCCHK(rehash_paths(own, U));
     HIPCHK(hipStreamSynchronize(st));
@@ -223,7 +223,7 @@ static int32_t tree_insert_incremental(dapol_tree_owned* own, const HostLeaves& 
     TreeInsArgs I{k, H, (const uint64_t*)(d + o_idx), (const uint64_t*)(d + o_v), (const uint32_t*)(d + o_r), (const uint32_t*)(d + o_m),
                   (const uint32_t*)(d + o_new), (uint32_t*)(d + o_pos), (int32_t*)(d + o_dP), (uint64_t*)(d + o_dv), (uint32_t*)(d + o_dr),
                   (const uint32_t*)(d + o_seed)};
-    hipLaunchKernelGGL(k_tree_ins_chain, dim3((unsigned)k), dim3(64), 0, st, ctx->tv, own->d_views.p, I);
+    LAUNCH_DX(ctx->tv.digest, (k_tree_ins_chain<DX>), dim3((unsigned)k), dim3(64), 0, st, ctx->tv, own->d_views.p, I);
     LAUNCH_CHECK();
     TreeUpdArgs U{k, H, (const uint64_t*)(d + o_idx), (const uint64_t*)(d + o_v), (const uint32_t*)(d + o_r), (uint32_t*)(d + o_pos), (int32_t*)(d + o_dP),
                   (uint64_t*)(d + o_dv), (uint32_t*)(d + o_dr), (uint32_t*)(d + o_flag), nullptr, (const uint32_t*)(d + o_m)};
@@ -284,17 +284,17 @@ static int32_t tree_insert_general(dapol_tree_owned* own, const HostLeaves& E, c
                      dw + plan.leaf_off, (const uint64_t*)(d + k * 8), (const uint32_t*)(d + k * 16), node_ext};
     hipLaunchKernelGGL(k_tree_ins_struct, dim3(nblk(n_new, 64)), dim3(64), 0, st, own->d_views.p, G);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_tree_ins_leaves, dim3(nblk(k, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, G);
+    LAUNCH_DX(ctx->tv.digest, (k_tree_ins_leaves<DX>), dim3(nblk(k, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, G);
     LAUNCH_CHECK();
     if (n_pad) {
-        hipLaunchKernelGGL(k_tree_edit_pad<true>, dim3(nblk(n_pad, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, n_pad, dw + plan.pad_lvl_off, dw + plan.pad_pos_off,
+        LAUNCH_DX(ctx->tv.digest, (k_tree_edit_pad<true, DX>), dim3(nblk(n_pad, 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, n_pad, dw + plan.pad_lvl_off, dw + plan.pad_pos_off,
                            dw /* the pad seed */, pad_ext);
         LAUNCH_CHECK();
     }
     for (int t = 0; t < H; t++) {
         const size_t n = plan.merge[t + 1].size() / 5;
         if (!n) continue;
-        hipLaunchKernelGGL(k_tree_edit_merge<true>, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + plan.merge_off[t + 1],
+        LAUNCH_DX(ctx->tv.digest, (k_tree_edit_merge<true, DX>), dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + plan.merge_off[t + 1],
                            node_ext + (size_t)(t & 1) * slots * 40, node_ext + (size_t)((t + 1) & 1) * slots * 40, pad_ext);
         LAUNCH_CHECK();
     }
@@ -357,14 +357,14 @@ static int32_t tree_remove_incremental(dapol_tree_owned* own, const std::vector<
     RCCHK(adopt_levels(own, staged, hv));
     // R2: the chain tops' siblings take their padding nodes; R3: the touched survivors, bottom-up
     if (!plan.pad_pos.empty()) {
-        hipLaunchKernelGGL(k_tree_edit_pad<false>, dim3(nblk(plan.pad_pos.size(), 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, plan.pad_pos.size(),
+        LAUNCH_DX(ctx->tv.digest, (k_tree_edit_pad<false, DX>), dim3(nblk(plan.pad_pos.size(), 64)), dim3(64), 0, st, ctx->tv, own->d_views.p, plan.pad_pos.size(),
                            (const uint8_t*)(d + o_lvl), dw + plan.pad_off, dw /* the pad seed */, (int32_t*)nullptr);
         LAUNCH_CHECK();
     }
     for (int t = 0; t < H; t++) {
         const size_t n = plan.merge[t + 1].size() / 2;
         if (!n) continue;
-        hipLaunchKernelGGL(k_tree_edit_merge<false>, dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + plan.merge_off[t + 1],
+        LAUNCH_DX(ctx->tv.digest, (k_tree_edit_merge<false, DX>), dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, hv[t], hv[t + 1], n, dw + plan.merge_off[t + 1],
                            (const int32_t*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr);
         LAUNCH_CHECK();
     }

@@ -542,13 +542,13 @@ static int32_t verify_upload_and_paths(dapol_ctx* ctx, ForkGuard& fg, int32_t he
     }
     // few proofs: a wavefront per path (latency); many: a lane per path (3x less work per path)
     if (ctx_wide(ctx))                                           // 64-byte node hashes: the lane kernel (a wavefront's shuffled hash chain is a 32-byte affair)
-        hipLaunchKernelGGL(k_verify_paths<16>, dim3(nblk(b, 64)), dim3(64), 0, sp, ctx->tv.digest, b, height, dl, dLC, dLH, dPC, dPH, droot, droot + 8,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify_paths<16, DG_RUNTIME>), dim3(nblk(b, 64)), dim3(64), 0, sp, ctx->tv.digest, b, height, dl, dLC, dLH, dPC, dPH, droot, droot + 8,
                            g_wire.siblings_leaf_first, dpath);
     else if (few)
-        hipLaunchKernelGGL(k_verify_paths_wave<8>, dim3((unsigned)b), dim3(64), 0, sp, ctx->tv.digest, b, height, dl, dLC, dLH, dPC, dPH, droot,
+        LAUNCH_DX(ctx->tv.digest, (k_verify_paths_wave<8, DX>), dim3((unsigned)b), dim3(64), 0, sp, ctx->tv.digest, b, height, dl, dLC, dLH, dPC, dPH, droot,
                            droot + 8, g_wire.siblings_leaf_first, dpath);
     else
-        hipLaunchKernelGGL(k_verify_paths<8>, dim3(nblk(b, 64)), dim3(64), 0, sp, ctx->tv.digest, b, height, dl, dLC, dLH, dPC, dPH, droot, droot + 8,
+        LAUNCH_DX(ctx->tv.digest, (k_verify_paths<8, DX>), dim3(nblk(b, 64)), dim3(64), 0, sp, ctx->tv.digest, b, height, dl, dLC, dLH, dPC, dPH, droot, droot + 8,
                            g_wire.siblings_leaf_first, dpath);
     LAUNCH_CHECK();
     if (side_paths) { HIPCHK(hipEventRecord(ctx->ev_join[2], sp)); FAULT_AFTER_FORK("verify_paths"); }

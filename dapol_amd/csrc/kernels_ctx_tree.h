@@ -220,7 +220,9 @@ struct LevelView {
 
 // ----------------------------------------------------------------------------------------- node routines
 // What a DAPOL node is, once: every kernel below -- the build, its small-tree phases and the in-place edits -- makes its leaves,
-// padding nodes and parents with these, so that all paths leave the same bytes.
+// padding nodes and parents with these, so that all paths leave the same bytes.  The routines that hash, and the kernels that call
+// them, are templates over DX (hash.h): DG_RUNTIME = the node digest is tbl.digest / `digest`, one of the three BLAKE ones, as these
+// kernels always read it; DG_SHA256 / DG_SHA3_256 = that digest, an instantiation of its own that no other context launches.
 // Leaf, DapolNode::new (src/dapol/node.rs:29-45): P = v*B + r*B_blinding, c = its encoding, h = D(c).  r: eight words with bit 255
 // already cleared by the caller (Scalar::from_bits); may be >= l.
 __device__ __forceinline__ void leaf_point(ge_p3& P, const TableView& tbl, uint64_t v, const uint32_t* r) {
@@ -228,13 +230,15 @@ __device__ __forceinline__ void leaf_point(ge_p3& P, const TableView& tbl, uint6
     tbl_fixed_mul_add_u64(P, tbl, tbl.row_B(0), v);
     tbl_fixed_mul_add(P, tbl, tbl.row_Bb(0), r);
 }
+template <int DX>
 __device__ __forceinline__ void leaf_encode(uint32_t* c, uint32_t* h, const TableView& tbl, const ge_p3& P) {
     ge_compress(c, P);
-    node_hash32(tbl.digest, h, c);
+    node_hash32_x<DX>(tbl.digest, h, c);
 }
+template <int DX>
 __device__ __forceinline__ void leaf_node(ge_p3& P, uint32_t* c, uint32_t* h, const TableView& tbl, uint64_t v, const uint32_t* r) {
     leaf_point(P, tbl, v, r);
-    leaf_encode(c, h, tbl, P);
+    leaf_encode<DX>(c, h, tbl, P);
 }
 // Padding node, Paddable::padding (node.rs:86-88): new(0, r) with r drawn for the node's position (seed mode) or read from the
 // caller's tape.  padding_draw = the positional 64-byte draw; padding_from_wide = the node of a draw: rm / rB = its blinding reduced
@@ -244,23 +248,26 @@ __device__ __forceinline__ void padding_draw(uint32_t* wide, const uint32_t* pad
     for (int k = 0; k < 8; k++) seed[k] = pad_seed[k];
     seed_wide(wide, seed, 1u, level, index);
 }
+template <int DX>
 __device__ __forceinline__ void padding_from_wide(ge_p3& pB, sc& rm, uint32_t* rB, uint32_t* cB, uint32_t* hB, const TableView& tbl, const uint32_t* wide) {
     sc_from_wide(rm, wide);
     sc_from_mont(rB, rm);
     ge_identity(pB);
     tbl_fixed_mul_add(pB, tbl, tbl.row_Bb(0), rB);
     ge_compress(cB, pB);
-    node_hash32(tbl.digest, hB, cB);
+    node_hash32_x<DX>(tbl.digest, hB, cB);
 }
+template <int DX>
 __device__ __forceinline__ void padding_from_wide(ge_p3& pB, uint32_t* rB, uint32_t* cB, uint32_t* hB, const TableView& tbl, const uint32_t* wide) {
     sc rm;
-    padding_from_wide(pB, rm, rB, cB, hB, tbl, wide);
+    padding_from_wide<DX>(pB, rm, rB, cB, hB, tbl, wide);
 }
+template <int DX>
 __device__ __forceinline__ void padding_node(ge_p3& pB, uint32_t* rB, uint32_t* cB, uint32_t* hB, const TableView& tbl, const uint32_t* pad_seed, uint64_t level,
                                              uint64_t index) {
     uint32_t wide[16];
     padding_draw(wide, pad_seed, level, index);
-    padding_from_wide(pB, rB, cB, hB, tbl, wide);
+    padding_from_wide<DX>(pB, rB, cB, hB, tbl, wide);
 }
 // The padding sibling of real node i of level L is kept beside it.
 __device__ __forceinline__ void store_pad_record(const LevelView& L, size_t i, const uint32_t* cB, const uint32_t* hB, const uint32_t* rB) {
@@ -297,16 +304,18 @@ __device__ __forceinline__ void sc_add_words(uint32_t* rp, const uint32_t* rA, c
     sc_add(ms, ma, mb);
     sc_from_mont(rp, ms);
 }
+template <int DX>
 __device__ __forceinline__ void parent_hash(int digest, uint32_t* hp, bool a_is_left, const uint32_t* cA, const uint32_t* cB, const uint32_t* hA, const uint32_t* hB) {
-    if (a_is_left) node_hash128(digest, hp, cA, cB, hA, hB);
-    else node_hash128(digest, hp, cB, cA, hB, hA);
+    if (a_is_left) node_hash128_x<DX>(digest, hp, cA, cB, hA, hB);
+    else node_hash128_x<DX>(digest, hp, cB, cA, hB, hA);
 }
+template <int DX>
 __device__ __forceinline__ void merge_parent(ge_p3& pp, uint32_t* rp, uint32_t* cp, uint32_t* hp, int digest, bool a_is_left, const ge_p3& pA, const ge_p3& pB,
                                              const uint32_t* rA, const uint32_t* rB, const uint32_t* cA, const uint32_t* cB, const uint32_t* hA, const uint32_t* hB) {
     sc_add_words(rp, rA, rB);
     ge_add(pp, pA, pB);
     ge_compress(cp, pp);
-    parent_hash(digest, hp, a_is_left, cA, cB, hA, hB);
+    parent_hash<DX>(digest, hp, a_is_left, cA, cB, hA, hB);
 }
 // Lower bound of `want` in the sorted idx[0 .. n).
 __device__ __forceinline__ size_t lower_bound_u64(const uint64_t* idx, size_t n, uint64_t want) {
@@ -320,6 +329,7 @@ __device__ __forceinline__ size_t lower_bound_u64(const uint64_t* idx, size_t n,
 
 // ------------------------------------------------------------------------------------------- commitments
 // One lane per node: leaf_node of (v[i], r[i]); bit 255 of r is ignored.
+template <int DX>
 __global__ __launch_bounds__(256) void k_commit_hash(TableView tbl, size_t n, const uint64_t* v, uint32_t* r, uint32_t* C,
                                                      uint32_t* H, int32_t* ext) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -332,7 +342,7 @@ __global__ __launch_bounds__(256) void k_commit_hash(TableView tbl, size_t n, co
     }
     ge_p3 acc;
     uint32_t c[8], h[8];
-    leaf_node(acc, c, h, tbl, v[i], rw);
+    leaf_node<DX>(acc, c, h, tbl, v[i], rw);
     st8(C + i * 8, c);
     st8(H + i * 8, h);
     if (ext) st_p3(ext + i * 40, acc);
@@ -353,7 +363,7 @@ struct PadTape {
 // SPLIT = 1 (the default since round 6; DAPOL_TREE_SPLIT=0 turns it off): the padding children of the level were made by k_tree_pad_level just before --
 // their records are read from padC / padH / padr and their points from extpad[q] -- so that neither kernel holds a fixed-base
 // product, two encodings and three hashes in one register allocation.
-template <int SPLIT>
+template <int SPLIT, int DX>
 __global__ __launch_bounds__(256) void k_tree_merge(TableView tbl, LevelView cur, LevelView nxt, const uint32_t* head, int level,
                                                     const uint32_t* pad_seed /*8 words*/, const uint32_t* cnt /*[levels + 1], device*/, PadTape tape,
                                                     const int32_t* extpad) {
@@ -395,14 +405,14 @@ __global__ __launch_bounds__(256) void k_tree_merge(TableView tbl, LevelView cur
         } else {
             padding_draw(wide, pad_seed, (uint64_t)level, my_idx ^ 1ull);
         }
-        padding_from_wide(pB, rB, cB, hB, tbl, wide);
+        padding_from_wide<DX>(pB, rB, cB, hB, tbl, wide);
         store_pad_record(cur, i, cB, hB, rB);
         cur.has_pad[i] = 1;
     }
     cur.parent[i] = (uint32_t)q;
     uint32_t rp[8], cp[8], hp[8];
     ge_p3 pp;
-    merge_parent(pp, rp, cp, hp, tbl.digest, pair || ((my_idx & 1ull) == 0), pA, pB, rA, rB, cA, cB, hA, hB);
+    merge_parent<DX>(pp, rp, cp, hp, tbl.digest, pair || ((my_idx & 1ull) == 0), pA, pB, rA, rB, cA, cB, hA, hB);
     nxt.idx[q] = my_idx >> 1;
     nxt.v[q] = vA + vB;           // u64 wrap == release-mode Rust (node.rs:72)
     st8(nxt.r + q * 8, rp);
@@ -412,6 +422,7 @@ __global__ __launch_bounds__(256) void k_tree_merge(TableView tbl, LevelView cur
 }
 
 // The padding children of one level on their own (seed mode): Paddable::padding for every parent q whose second child is not real.
+template <int DX>
 __global__ __launch_bounds__(256) void k_tree_pad_level(TableView tbl, LevelView cur, const uint32_t* head, int level, const uint32_t* pad_seed,
                                                         const uint32_t* cnt, int32_t* extpad) {
     size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -422,19 +433,20 @@ __global__ __launch_bounds__(256) void k_tree_pad_level(TableView tbl, LevelView
     if ((i + 1 < cur_n) && (cur.idx[i + 1] == (my_idx ^ 1ull))) return;
     uint32_t rB[8], cB[8], hB[8];
     ge_p3 pB;
-    padding_node(pB, rB, cB, hB, tbl, pad_seed, (uint64_t)level, my_idx ^ 1ull);
+    padding_node<DX>(pB, rB, cB, hB, tbl, pad_seed, (uint64_t)level, my_idx ^ 1ull);
     store_pad_record(cur, i, cB, hB, rB);
     st_p3(extpad + q * 40, pB);
 }
 
 // The padding nodes of n given positions (level[i], index[i]), as records.
+template <int DX>
 __global__ void k_padding_nodes(TableView tbl, size_t n, const uint32_t* pad_seed, const uint8_t* level, const uint64_t* index, uint32_t* C,
                                 uint32_t* H, uint32_t* r) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t rB[8], cB[8], hB[8];
     ge_p3 p;
-    padding_node(p, rB, cB, hB, tbl, pad_seed, (uint64_t)level[i], index[i]);
+    padding_node<DX>(p, rB, cB, hB, tbl, pad_seed, (uint64_t)level[i], index[i]);
     st8(C + i * 8, cB);
     st8(H + i * 8, hB);
     st8(r + i * 8, rB);
@@ -500,6 +512,7 @@ __global__ __launch_bounds__(64) void k_tree_find_paths(const LevelView* views, 
     pos[F.height] = (uint32_t)p;
     if (hp) hp[F.height] = 0;
 }
+template <int DX>
 __global__ __launch_bounds__(64) void k_tree_upd_leaves(TableView tbl, const LevelView* views, TreeUpdArgs U) {
     const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (j >= U.k) return;
@@ -522,7 +535,7 @@ __global__ __launch_bounds__(64) void k_tree_upd_leaves(TableView tbl, const Lev
     sc_sub(md, mn, mo);
     for (int i = 0; i < 8; i++) U.dr[j * 8 + i] = md.v[i];
     U.dv[j] = U.v[j] - L0.v[lo];
-    leaf_encode(c, h, tbl, pn);                    // (after the delta: the old encoding's words are free by now)
+    leaf_encode<DX>(c, h, tbl, pn);                    // (after the delta: the old encoding's words are free by now)
     L0.v[lo] = U.v[j];
     st8(L0.r + lo * 8, rn);
     st8(L0.C + lo * 8, c);
@@ -567,6 +580,7 @@ __global__ __launch_bounds__(64) void k_tree_upd_nodes(const LevelView* views, T
     st8(L.r + (size_t)p * 8, rr);
 }
 // grid = 1 block of up to 1,024 threads; thread j = update j (k <= 1,024), stepping through the levels together.
+template <int DX>
 __global__ __launch_bounds__(1024) void k_tree_upd_hash(int digest, const LevelView* views, TreeUpdArgs U, int level_begin, int level_end) {
     const size_t j = threadIdx.x + (size_t)blockIdx.x * blockDim.x;
     const size_t stride = (size_t)U.height + 1;
@@ -581,7 +595,7 @@ __global__ __launch_bounds__(1024) void k_tree_upd_hash(int digest, const LevelV
                 ld8(cA, L.C + i * 8); ld8(hA, L.H + i * 8);
                 const bool left = (my & 1ull) == 0;
                 load_other_child(cB, hB, nullptr, nullptr, L, i, left);
-                parent_hash(digest, hp, left, cA, cB, hA, hB);
+                parent_hash<DX>(digest, hp, left, cA, cB, hA, hB);
                 st8(views[k + 1].H + (size_t)pp * 8, hp);
             }
         }
@@ -687,6 +701,7 @@ struct TreeInsArgs {
     const uint32_t* pad_seed;                                       // [8]
 };
 // one wavefront per new leaf; lane t < m handles chain node t
+template <int DX>
 __global__ __launch_bounds__(64) void k_tree_ins_chain(TableView tbl, const LevelView* views, TreeInsArgs I) {
     const size_t j = blockIdx.x;
     const int t = threadIdx.x, m = (int)I.m[j];
@@ -710,7 +725,7 @@ __global__ __launch_bounds__(64) void k_tree_ins_chain(TableView tbl, const Leve
     if (has_pad) {
         uint32_t wide[16];
         padding_draw(wide, I.pad_seed, (uint64_t)t, (x >> t) ^ 1ull);
-        padding_from_wide(Pp, rp, rB, cB, hB, tbl, wide);
+        padding_from_wide<DX>(Pp, rp, rB, cB, hB, tbl, wide);
     }
     // inclusive prefix sums over the lanes: S_t = sum_{u <= t} pad(u) (points and blindings); chain node t = leaf + S_{t-1}
     ge_p3 S = Pp;
@@ -746,7 +761,7 @@ __global__ __launch_bounds__(64) void k_tree_ins_chain(TableView tbl, const Leve
     L.v[d] = I.v[j];
     st8(L.r + d * 8, t == 0 ? rl : rN);             // a leaf keeps its blinding as given (possibly >= l); parents hold the reduced sum
     st8(L.C + d * 8, cN);
-    if (t == 0) { node_hash32(tbl.digest, hN, cN); st8(L.H + d * 8, hN); }       // (parents' hashes: k_tree_upd_hash, level by level)
+    if (t == 0) { node_hash32_x<DX>(tbl.digest, hN, cN); st8(L.H + d * 8, hN); }       // (parents' hashes: k_tree_upd_hash, level by level)
     L.has_pad[d] = has_pad ? 1 : 0;
     if (has_pad) store_pad_record(L, d, cB, hB, rB);
     L.parent[d] = np[t + 1];
@@ -815,6 +830,7 @@ __global__ __launch_bounds__(64) void k_tree_ins_struct(const LevelView* views, 
     if (G.sib[i] != 0xffffffffu) L.has_pad[G.sib[i]] = 0;          // a chain top: S's padding sibling (at this node's position) goes away
 }
 // J4
+template <int DX>
 __global__ __launch_bounds__(64) void k_tree_ins_leaves(TableView tbl, const LevelView* views, TreeInsGeneral G) {
     const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (j >= G.k) return;
@@ -824,7 +840,7 @@ __global__ __launch_bounds__(64) void k_tree_ins_leaves(TableView tbl, const Lev
     ld8(rl, G.r + j * 8);
     rl[7] &= 0x7fffffffu;                          // Scalar::from_bits; the leaf keeps its blinding as given (possibly >= l)
     ge_p3 P0;
-    leaf_node(P0, c, h, tbl, G.v[j], rl);
+    leaf_node<DX>(P0, c, h, tbl, G.v[j], rl);
     L.v[d] = G.v[j];
     st8(L.r + d * 8, rl);
     st8(L.C + d * 8, c);
@@ -834,7 +850,7 @@ __global__ __launch_bounds__(64) void k_tree_ins_leaves(TableView tbl, const Lev
 // J5 and R2 of the removal (below): real node pos[i] of level level[i] gains its padding sibling.  KEEP_EXT: the padding node's
 // extended point stays in ext[i] for the merges above it.  LevelT is deduced from the plan's level list -- bytes in the removal's, words
 // in the insert's -- so the two instantiations the stage lists call <0> and <1> are <false, uint8_t> and <true, uint32_t> in the code object.
-template <bool KEEP_EXT, typename LevelT>
+template <bool KEEP_EXT, int DX, typename LevelT>
 __global__ __launch_bounds__(64) void k_tree_edit_pad(TableView tbl, const LevelView* views, size_t n, const LevelT* level, const uint32_t* pos,
                                                       const uint32_t* pad_seed, int32_t* ext) {
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -844,7 +860,7 @@ __global__ __launch_bounds__(64) void k_tree_edit_pad(TableView tbl, const Level
     const LevelView L = views[t];
     uint32_t rB[8], cB[8], hB[8];
     ge_p3 pB;
-    padding_node(pB, rB, cB, hB, tbl, pad_seed, (uint64_t)t, L.idx[s] ^ 1ull);
+    padding_node<DX>(pB, rB, cB, hB, tbl, pad_seed, (uint64_t)t, L.idx[s] ^ 1ull);
     store_pad_record(L, s, cB, hB, rB);
     L.has_pad[s] = 1;
     if (KEEP_EXT) st_p3(ext + i * 40, pB);
@@ -854,7 +870,7 @@ __global__ __launch_bounds__(64) void k_tree_edit_pad(TableView tbl, const Level
 // pairs them.  SLOTS = false (removal, 2 words a record): both children's points are decoded from their encodings, which are the
 // tree's own and always decode.  SLOTS = true (insert, 5 words): | the node's slot | the child's slot | the other child: a slot of
 // cur's half, 0x80000000 | pad slot, or 0xffffffff = decode it; the node's point is left in its slot.
-template <bool SLOTS>
+template <bool SLOTS, int DX>
 __global__ __launch_bounds__(64) void k_tree_edit_merge(int digest, LevelView cur, LevelView nxt, size_t n, const uint32_t* e, const int32_t* ext_cur,
                                                         int32_t* ext_nxt, const int32_t* pad_ext) {
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -879,7 +895,7 @@ __global__ __launch_bounds__(64) void k_tree_edit_merge(int digest, LevelView cu
         (void)ge_decompress(pB, cB);
     }
     uint32_t rp[8], cp[8], hp[8];
-    merge_parent(pp, rp, cp, hp, digest, left, pA, pB, rA, rB, cA, cB, hA, hB);
+    merge_parent<DX>(pp, rp, cp, hp, digest, left, pA, pB, rA, rB, cA, cB, hA, hB);
     nxt.v[p] = vA + vB;                            // u64 wrap == release-mode Rust (node.rs:72)
     st8(nxt.r + p * 8, rp);
     st8(nxt.C + p * 8, cp);
@@ -977,6 +993,7 @@ __device__ __forceinline__ int tree_level_of(size_t t, const uint32_t* lvl_off, 
     while (k + 1 < nlev && t >= lvl_off[k + 1]) k++;
     return k;
 }
+template <int DX>
 __global__ __launch_bounds__(64) void k_tree_padding_all(TableView tbl, const LevelView* views, int height, const uint32_t* cnt, const uint32_t* lvl_off,
                                                         const uint32_t* pad_seed, int32_t* extpad) {
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -987,7 +1004,7 @@ __global__ __launch_bounds__(64) void k_tree_padding_all(TableView tbl, const Le
     if (i >= cnt[level] || !cur.has_pad[i]) return;
     uint32_t rB[8], cB[8], hB[8];
     ge_p3 pB;
-    padding_node(pB, rB, cB, hB, tbl, pad_seed, (uint64_t)level, cur.idx[i] ^ 1ull);
+    padding_node<DX>(pB, rB, cB, hB, tbl, pad_seed, (uint64_t)level, cur.idx[i] ^ 1ull);
     store_pad_record(cur, i, cB, hB, rB);
     st_p3(extpad + t * 40, pB);
 }
@@ -1030,6 +1047,7 @@ __global__ __launch_bounds__(64) void k_tree_compress_all(const LevelView* views
     ge_compress(c, p);
     st8(views[level].C + q * 8, c);
 }
+template <int DX>
 __global__ __launch_bounds__(64) void k_tree_hash_level(int digest, LevelView cur, LevelView nxt, int level, const uint32_t* cnt) {
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= cnt[level]) return;
@@ -1040,7 +1058,7 @@ __global__ __launch_bounds__(64) void k_tree_hash_level(int digest, LevelView cu
     ld8(cA, cur.C + i * 8);
     ld8(hA, cur.H + i * 8);
     load_other_child(cB, hB, nullptr, nullptr, cur, i, true);        // (this lane is the left node of a pair, or has a padding sibling)
-    parent_hash(digest, hp, pair || (cur.idx[i] & 1ull) == 0, cA, cB, hA, hB);
+    parent_hash<DX>(digest, hp, pair || (cur.idx[i] & 1ull) == 0, cA, cB, hA, hB);
     st8(nxt.H + (size_t)q * 8, hp);
 }
 
@@ -1172,7 +1190,7 @@ template <int HW>
 __device__ __forceinline__ void ldh(uint32_t* w, const uint32_t* p) { ld8(w, p); if (HW == 16) ld8(w + 8, p + 8); }
 template <int HW>
 __device__ __forceinline__ void sth(uint32_t* p, const uint32_t* w) { st8(p, w); if (HW == 16) st8(p + 8, w + 8); }
-template <int HW>
+template <int HW, int DX>
 __global__ void k_merge_records(int dg, size_t n, const uint32_t* CL, const uint32_t* HL, const uint64_t* vL, const uint32_t* rL,
                                 const uint32_t* CR, const uint32_t* HR, const uint64_t* vR, const uint32_t* rR, uint32_t* C, uint32_t* H,
                                 uint64_t* v, uint32_t* r, uint32_t* bad) {
@@ -1185,7 +1203,7 @@ __global__ void k_merge_records(int dg, size_t n, const uint32_t* CL, const uint
     if (!ok) { atomicOr(bad, 1u); return; }
     ge_add(p, a, b);
     ge_compress(cp, p);
-    node_hash_parent_w<HW>(dg, hp, cl, cr, hl, hr);
+    node_hash_parent_w<HW, DX>(dg, hp, cl, cr, hl, hr);
     st8(C + i * 8, cp);
     sth<HW>(H + i * HW, hp);
     if (v) {

@@ -19,6 +19,8 @@
 
 namespace dapol {
 
+// The kernels that hash are templates over the streaming state D of the digest (hash.h): Digest for BLAKE3 and Blake2s (by A.kind),
+// Sha256Stream, Sha3Stream.
 enum { LEAF_MAX_RETRIES = 128 };            // MAX_INDEX_RETRIES, src/dapol/mod.rs:29
 
 struct LeafArgs {
@@ -55,10 +57,11 @@ __device__ __forceinline__ bool leaf_occupied(const LeafOccupied& O, uint64_t x)
     return lo < O.n && O.idx[lo] == x;
 }
 
+template <class D>
 __global__ __launch_bounds__(64) void k_leaf_hash(LeafArgs A) {
     size_t e = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (e >= A.n) return;
-    Digest d;
+    D d;
     uint32_t aid[8], st[8], bl[8];
     uint32_t stack[B3_STACK_DEPTH * 8];                  // ids of any length (mod.rs:347-349, 358-360): BLAKE3 beyond one chunk chains
                                                          // its chunks through this stack (private memory, touched by long inputs only)
@@ -166,6 +169,7 @@ __device__ inline uint32_t heap_pop(uint32_t* h, uint32_t& n) {
 }
 // One lane, input order: every unresolved entity re-hashes until it finds a slot that no EARLIER entity holds;
 // a later entity sitting on that slot is evicted and re-queued (it comes later in the order, so it is still ahead).
+template <class D>
 __global__ void k_leaf_resolve(LeafArgs A, LeafResolve R) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     uint32_t hn = 0;
@@ -178,7 +182,7 @@ __global__ void k_leaf_resolve(LeafArgs A, LeafResolve R) {
         for (int i = 0; i < 8; i++) st[i] = A.idx_state[(size_t)e * 8 + i];
         bool placed = false;
         for (int tries = 1; tries < A.max_tries && !placed; tries++) {      // the first try was the sorted candidate
-            Digest d;
+            D d;
             dg_init(d, A.kind);
             dg_update_words(d, st, 8);
             dg_final(d, st);
@@ -246,6 +250,7 @@ __global__ void k_leaf_claim_first(LeafArgs A, LeafTable T) {
     T.tries[e] = 1;
 }
 // One round: every entity whose slot now belongs to an earlier entity draws candidates until it owns one (for now).
+template <class D>
 __global__ void k_leaf_settle(LeafArgs A, LeafTable T) {
     size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= A.n) return;
@@ -262,7 +267,7 @@ __global__ void k_leaf_settle(LeafArgs A, LeafTable T) {
             tries = (uint32_t)A.max_tries + 1;
             break;
         }
-        Digest d;
+        D d;
         dg_init(d, A.kind);
         dg_update_words(d, st, 8);
         dg_final(d, st);
@@ -291,6 +296,7 @@ __global__ void k_leaf_claim_first_onto(LeafArgs A, LeafTable T, LeafOccupied O)
     T.pos[e] = hp;
     T.tries[e] = 1;
 }
+template <class D>
 __global__ void k_leaf_settle_onto(LeafArgs A, LeafTable T, LeafOccupied O) {
     size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= A.n) return;
@@ -307,7 +313,7 @@ __global__ void k_leaf_settle_onto(LeafArgs A, LeafTable T, LeafOccupied O) {
             tries = (uint32_t)A.max_tries + 1;
             break;
         }
-        Digest d;
+        D d;
         dg_init(d, A.kind);
         dg_update_words(d, st, 8);
         dg_final(d, st);

@@ -1224,7 +1224,7 @@ __global__ void k_rvb_verdicts(VerifyArgs V) {
 // HW = words of a node hash (8: the 32-byte digests; 16: Blake2b-512 -- hash arrays then hold 16 words per node).
 template <int HW>
 __device__ __forceinline__ void ldhw(uint32_t* w, const uint32_t* p) { ld8(w, p); if (HW == 16) ld8(w + 8, p + 8); }
-template <int HW>
+template <int HW, int DX>
 __global__ __launch_bounds__(64) void k_verify_paths(int dg, size_t b, int height, const uint64_t* leaf_idx, const uint32_t* leafC, const uint32_t* leafH,
                                                     const uint32_t* pC, const uint32_t* pH, const uint32_t* rootC, const uint32_t* rootH,
                                                     int leaf_first, uint8_t* ok) {
@@ -1241,8 +1241,8 @@ __global__ __launch_bounds__(64) void k_verify_paths(int dg, size_t b, int heigh
         ld8(sc_, pC + slot * 8);
         ldhw<HW>(sh, pH + slot * HW);
         good &= ge_decompress(sp, sc_);                      // deserialisation rejects non-canonical points (proof/node.rs:88-94)
-        if ((idx >> k) & 1) node_hash_parent_w<HW>(dg, hn, sc_, c, sh, h);
-        else node_hash_parent_w<HW>(dg, hn, c, sc_, h, sh);
+        if ((idx >> k) & 1) node_hash_parent_w<HW, DX>(dg, hn, sc_, c, sh, h);
+        else node_hash_parent_w<HW, DX>(dg, hn, c, sc_, h, sh);
         ge_p3 t;
         ge_add(t, acc, sp);
         acc = t;
@@ -1258,7 +1258,7 @@ __global__ __launch_bounds__(64) void k_verify_paths(int dg, size_t b, int heigh
 // version above is a chain of `height` decompressions, additions and encodings -- 4.9 ms for one height-32 path.  Here lane k
 // decompresses sibling k, an inclusive prefix sum over the lanes (shuffles) gives every ancestor's commitment at once, each lane
 // encodes its own, and only the hash chain stays serial (every lane walks it in step; its inputs come by shuffle).
-template <int HW>
+template <int HW, int DX>
 __global__ __launch_bounds__(64) void k_verify_paths_wave(int dg, size_t b, int height, const uint64_t* leaf_idx, const uint32_t* leafC,
                                                          const uint32_t* leafH, const uint32_t* pC, const uint32_t* pH, const uint32_t* rootC,
                                                          const uint32_t* rootH, int leaf_first, uint8_t* ok) {
@@ -1303,8 +1303,8 @@ __global__ __launch_bounds__(64) void k_verify_paths_wave(int dg, size_t b, int 
             nx[i] = (uint32_t)__shfl((int)cn[i], k, 64);
         }
         for (int i = 0; i < HW; i++) shk[i] = (uint32_t)__shfl((int)sh[i], k, 64);
-        if ((idx >> k) & 1) node_hash_parent_w<HW>(dg, hn, sk, c, shk, h);
-        else node_hash_parent_w<HW>(dg, hn, c, sk, h, shk);
+        if ((idx >> k) & 1) node_hash_parent_w<HW, DX>(dg, hn, sk, c, shk, h);
+        else node_hash_parent_w<HW, DX>(dg, hn, c, sk, h, shk);
         for (int i = 0; i < 8; i++) c[i] = nx[i];
         for (int i = 0; i < HW; i++) h[i] = hn[i];
     }

@@ -28,7 +28,7 @@ struct TableView {
     const int32_t* base;   // device pointer
     int32_t max_parties;
     int32_t wbits;         // W
-    int32_t digest;        // node hash D of the context: DG_BLAKE3 (0) or DG_BLAKE2S (1)
+    int32_t digest;        // node hash D of the context: a DG_* kind of hash.h (= the DAPOL_DIGEST_* id)
     // High-half rows (0 = none): a second row per G / H generator holding the multiples of 2^(W * hi_split) * P, so that a sum
     // whose accumulators cannot share doublings (the materialisation of the folded generators: one accumulator per lane, 255
     // doublings for 480 additions) walks hi_split windows instead of nwin_c(): the scalar is split s = s_lo + 2^(W hi_split) s_hi

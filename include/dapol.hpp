@@ -60,7 +60,7 @@ struct DapolNode {
 
 class Context {                                // PedersenGens::default() + BulletproofGens::new(64, m), once
   public:
-    // digest = the node hash D of Dapol<D, R>: DAPOL_DIGEST_BLAKE3 or DAPOL_DIGEST_BLAKE2S.  This mirror's node types carry 32-byte
+    // digest = the node hash D of Dapol<D, R>: DAPOL_DIGEST_BLAKE3, DAPOL_DIGEST_BLAKE2S, DAPOL_DIGEST_SHA256 or DAPOL_DIGEST_SHA3_256.  This mirror's node types carry 32-byte
     // hashes (Bytes32), like Dapol::new's DIGEST_SIZE check (src/dapol/mod.rs:101-103): the 64-byte DAPOL_DIGEST_BLAKE2B of the
     // new_blank + build path is served by the C ABI itself (include/dapol_hip.h), and is refused HERE before any buffer could be too small.
     // max_parties = the largest aggregation a proof may need, rounded up to a power of two: 32 serves trees up to height 32
@@ -75,7 +75,10 @@ class Context {                                // PedersenGens::default() + Bull
     dapol_options options() const { dapol_options o{}; check(dapol_ctx_get_options(h_, &o)); return o; }
     void set_options(dapol_options o) { o.struct_size = (int32_t)sizeof(dapol_options); check(dapol_ctx_set_options(h_, &o)); }
     ~Context() { dapol_ctx_destroy(h_); }
-    static void digest32(int digest) { if (digest != DAPOL_DIGEST_BLAKE3 && digest != DAPOL_DIGEST_BLAKE2S) throw DapolError(DAPOL_ERR_INVALID_DIGEST_SIZE); }
+    static void digest32(int digest) {
+        if (digest != DAPOL_DIGEST_BLAKE3 && digest != DAPOL_DIGEST_BLAKE2S && digest != DAPOL_DIGEST_SHA256 && digest != DAPOL_DIGEST_SHA3_256)
+            throw DapolError(DAPOL_ERR_INVALID_DIGEST_SIZE);
+    }
     Context(const Context&) = delete;
     Context& operator=(const Context&) = delete;
     dapol_ctx* get() const { return h_; }

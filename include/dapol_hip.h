@@ -71,14 +71,18 @@ enum { DAPOL_POLICY_PADDING = 0, DAPOL_POLICY_SPLITTING = 1 };  /* RangeProofPad
  * dapol_verify_entities / dapol_verify_batch, dapol_merge_batch, dapol_padding_nodes, dapol_commit_hash_batch.  What the reference
  * refuses for such a digest is refused here with DAPOL_ERR_INVALID_DIGEST_SIZE: Dapol::new (dapol_tree_build with enforce_sparsity,
  * dapol_build_leaf_nodes); so are the paths that exist only for the benchmark and for multi-GPU sharding (workloads, shard trees,
- * the communicator, node records), whose records carry 32-byte hashes. */
-enum { DAPOL_DIGEST_BLAKE3 = 0, DAPOL_DIGEST_BLAKE2S = 1, DAPOL_DIGEST_BLAKE2B = 2 };
+ * the communicator, node records), whose records carry 32-byte hashes.
+ * D = sha2::Sha256 (DAPOL_DIGEST_SHA256) and D = sha3::Sha3_256 (DAPOL_DIGEST_SHA3_256), the other two hash crates of the reference's
+ * manifest: 32-byte digests, so every path of a BLAKE3 context works with them unchanged, sharding, workloads, records, the wire
+ * format, the shared prover / re-prover / proof store / shared verifier and Dapol::new's leaf derivation included.
+ * Id 3 is reserved and refused like every other value. */
+enum { DAPOL_DIGEST_BLAKE3 = 0, DAPOL_DIGEST_BLAKE2S = 1, DAPOL_DIGEST_BLAKE2B = 2, /* 3: reserved */ DAPOL_DIGEST_SHA256 = 4, DAPOL_DIGEST_SHA3_256 = 5 };
 
 /* Replaces the per-call PedersenGens::default() (src/dapol/node.rs:31, src/range/mod.rs:49,65,84,103) and
  * BulletproofGens::new(64, m) (src/range/mod.rs:50,66,85,104): generators and their window tables are derived
  * ONCE, on the GPU, for up to max_parties parties of 64 bits.  max_parties must be a power of two <= 1024.
  * digest_id: the node hash D of Dapol<D, R> used by every tree / merge / verify call of this context; anything but the
- * three digests above -> DAPOL_ERR_INVALID_DIGEST_SIZE. */
+ * five digests above (3 included: reserved) -> DAPOL_ERR_INVALID_DIGEST_SIZE. */
 int32_t dapol_ctx_create(int32_t device, int32_t max_parties, int32_t digest_id, dapol_ctx** out);
 int32_t dapol_ctx_digest_bytes(dapol_ctx* ctx, int32_t* bytes);          /* D::output_size(): 32 or 64 -- the size of every node hash of this context */
 /* Settings of a context.  Every field: 0 = the library's own choice (what a plain dapol_ctx_create gives).  The first three are
@@ -148,8 +152,8 @@ int32_t dapol_commit_hash_batch(dapol_ctx* ctx, size_t n, const uint64_t* v, con
  * (ids as concatenated bytes with n+1 offsets) -> for every liability its tree index and blinding factor, returned both
  * per input entity (idx_by_entity, may be NULL = the id_to_idx_map of mod.rs:388) and sorted by index, ready for
  * dapol_tree_build (mod.rs:396): leaf_idx_sorted / v_sorted / r32_sorted, with order_sorted[p] = input position of the
- * p-th leaf.  digest_id: DAPOL_DIGEST_BLAKE3 or DAPOL_DIGEST_BLAKE2S (the digest of the reference's known-answer tests,
- * src/dapol/tests.rs:13,21); ids of any length, as in the reference (mod.rs:347-349, 358-360) -- BLAKE3 inputs beyond one
+ * p-th leaf.  digest_id: DAPOL_DIGEST_BLAKE3, DAPOL_DIGEST_BLAKE2S (the digest of the reference's known-answer tests,
+ * src/dapol/tests.rs:13,21), DAPOL_DIGEST_SHA256 or DAPOL_DIGEST_SHA3_256; ids of any length, as in the reference (mod.rs:347-349, 358-360) -- BLAKE3 inputs beyond one
  * 1024-byte chunk go through the tree mode on the device.  Collisions are resolved exactly as the
  * reference does (an entity competes only with the entities before it in the input; up to 128 re-hashes).
  * Errors: DAPOL_ERR_TREE_HEIGHT_TOO_BIG, DAPOL_ERR_SPARSITY_TOO_SMALL (2^height < 2n), DAPOL_ERR_DUPLICATED_INTERNAL_ID,
@@ -238,7 +242,7 @@ int32_t dapol_tree_insert(dapol_tree* tree, size_t k, const uint64_t* leaf_idx, 
  * those of the new liabilities in dapol_build_leaf_nodes(L ++ new); after removals they are the sequential rule over the leaves that
  * are left (a freed index can be taken again).  Candidates are looked up in the tree's leaf array on the device: the cost is k hash
  * chains and k log2(n_leaves) index reads, nothing of the tree's size is allocated, copied or scanned.
- * Errors, all with the tree untouched: DAPOL_ERR_INVALID_DIGEST_SIZE (digest_id not BLAKE3 / Blake2s), DAPOL_ERR_SPARSITY_TOO_SMALL
+ * Errors, all with the tree untouched: DAPOL_ERR_INVALID_DIGEST_SIZE (digest_id not BLAKE3 / Blake2s / SHA-256 / SHA3-256), DAPOL_ERR_SPARSITY_TOO_SMALL
  * (2^height < 2 (n_leaves + k): Dapol::new's rule on the joined count), DAPOL_ERR_DUPLICATED_INTERNAL_ID (an internal id twice IN THE
  * BATCH), DAPOL_ERR_FAILED_TO_MAP_INDEX (dapol_last_error names the position within the batch), DAPOL_ERR_INVALID_ARGUMENT for a
  * tree marked invalid and for a shard tree (dapol_tree_build_shard), whose leaf array is not the whole set of taken indexes.
