@@ -584,27 +584,70 @@ def _ip(a, b):
     return sum(x * y for x, y in zip(a, b)) % L
 
 
-def range_prove(values, blindings, n, tape: Tape, label=b"", commit_values=None, A_offset=0, info=None):
+FORGE_KINDS = ("value", "blinding", "bit", "a_R", "A", "S", "L_k", "R_k", "T1", "T2", "t_x", "tau", "mu", "a", "b")
+
+
+def _forge_point(forge, G, H):
+    """The point P in {B, B_blinding, G_q, H_q} a forged group element is moved along."""
+    which = forge.get("P", "B")
+    if which == "B":
+        return BASEPOINT
+    if which == "B_blinding":
+        return B_BLINDING
+    return {"G": G, "H": H}[which][forge["q"]]
+
+
+def range_prove(values, blindings, n, tape: Tape, label=b"", commit_values=None, A_offset=0, info=None, forge=None):
     """RangeProof::prove_multiple_with_rng with Transcript::new(label) (src/range/mod.rs:48-78 uses label=[]).
     Draw order per party j: a_blinding, s_blinding, s_L[0..n), s_R[0..n); then per party: t1_blinding, t2_blinding.
     Adversarial hooks for the soundness tests (never used by the honest paths): commit_values = the values the V_j commit
     to while the bits still come from `values` (an out-of-range statement with an otherwise honest proof); A_offset = kappa
-    puts A + kappa*B into the transcript and the proof; info (a dict) receives the challenges."""
+    puts A + kappa*B into the transcript and the proof; info (a dict) receives every challenge (y, z, x, w, u) and the
+    commitments V.
+
+    forge = dict(kind=, d=, party=j | q=generator index | k=round, P="B" | "B_blinding" | "G" | "H") makes ONE element wrong.  The
+    rule for every kind: the forged element is what enters the transcript and the proof, and everything after it is computed
+    honestly from the resulting challenges and the prover's own witness -- the proof is consistent in the transcript and wrong
+    in the algebra only.  Kinds (FORGE_KINDS): value (V_j commits to v_j + d), blinding (V_j commits under r_j + d), bit
+    (a_L[q] = 2, a_R[q] = 1, V commits to <a_L, 2^i>: only a_L o a_R = 0 is broken), a_R (a_R[q] = a_L[q] - 1 + d), A / S / L_k /
+    R_k (moved by d*P), T1 / T2 (moved by d*B or d*B_blinding), t_x / tau / mu and the final a / b (sent as value + d)."""
     m = len(values)
     assert n in (8, 16, 32, 64) and m & (m - 1) == 0 and m > 0 and len(blindings) == m
+    f = dict(forge) if forge else {}
+    kind, fd = f.get("kind"), f.get("d", 0) % L
+    assert kind is None or (kind in FORGE_KINDS and fd != 0)
     G, H = bp_gens(n, m)
     tr = Transcript(label)
     tr.rangeproof_domain_sep(n, m)
     # Party::new + assign_position_with_rng
     parties = []
-    Vs = [pedersen_commit(v, vb).compress() for v, vb in zip(commit_values if commit_values is not None else values, blindings)]
+    aLs = [[(v >> i) & 1 for i in range(n)] for v in values]
+    aRs = [[(a - 1) % L for a in row] for row in aLs]
+    cv = list(commit_values if commit_values is not None else values)
+    cb = list(blindings)
+    if kind == "value":
+        cv[f["party"]] += fd
+    elif kind == "blinding":
+        cb[f["party"]] += fd
+    elif kind == "bit":
+        j, i = divmod(f["q"], n)
+        aLs[j][i], aRs[j][i] = 2, 1
+        cv[j] = sum(a << k for k, a in enumerate(aLs[j]))
+    elif kind == "a_R":
+        j, i = divmod(f["q"], n)
+        aRs[j][i] = (aLs[j][i] - 1 + fd) % L
+    Vs = [pedersen_commit(v, vb).compress() for v, vb in zip(cv, cb)]
     tape.rekey(n, m, Vs)
     for j, (v, vb) in enumerate(zip(values, blindings)):
         V = Vs[j]
         a_bl = tape.scalar()
         A = a_bl * B_BLINDING
         for i in range(n):
-            A = A + (G[j * n + i] if (v >> i) & 1 else -H[j * n + i])
+            aL, aR = aLs[j][i], aRs[j][i]
+            if aL:
+                A = A + (G[j * n + i] if aL == 1 else aL * G[j * n + i])
+            if aR:
+                A = A + (-H[j * n + i] if aR == L - 1 else aR * H[j * n + i])
         s_bl = tape.scalar()
         s_L = [tape.scalar() for _ in range(n)]
         s_R = [tape.scalar() for _ in range(n)]
@@ -620,6 +663,10 @@ def range_prove(values, blindings, n, tape: Tape, label=b"", commit_values=None,
         S = S + p["S"]
     if A_offset:
         A = A + (A_offset % L) * BASEPOINT
+    if kind == "A":
+        A = A + fd * _forge_point(f, G, H)
+    if kind == "S":
+        S = S + fd * _forge_point(f, G, H)
     A_c, S_c = A.compress(), S.compress()
     tr.append_point(b"A", A_c)
     tr.append_point(b"S", S_c)
@@ -636,8 +683,8 @@ def range_prove(values, blindings, n, tape: Tape, label=b"", commit_values=None,
         l0, l1, r0, r1 = [], [], [], []
         exp_y, exp_2 = offset_y, 1
         for i in range(n):
-            a_L = (p["v"] >> i) & 1
-            a_R = (a_L - 1) % L
+            a_L = aLs[j][i]
+            a_R = aRs[j][i]
             l0.append((a_L - z) % L)
             l1.append(p["s_L"][i])
             r0.append((exp_y * (a_R + z) + offset_zz * exp_2) % L)
@@ -652,6 +699,10 @@ def range_prove(values, blindings, n, tape: Tape, label=b"", commit_values=None,
         p["t2_bl"] = tape.scalar()
         T1 = T1 + pedersen_commit(t1, p["t1_bl"])
         T2 = T2 + pedersen_commit(t2, p["t2_bl"])
+    if kind == "T1":
+        T1 = T1 + fd * _forge_point(f, G, H)
+    if kind == "T2":
+        T2 = T2 + fd * _forge_point(f, G, H)
     T1_c, T2_c = T1.compress(), T2.compress()
     tr.append_point(b"T_1", T1_c)
     tr.append_point(b"T_2", T2_c)
@@ -666,9 +717,9 @@ def range_prove(values, blindings, n, tape: Tape, label=b"", commit_values=None,
         mu += p["a_bl"] + p["s_bl"] * x
         l_vec += [(a + b * x) % L for a, b in zip(p["l0"], p["l1"])]
         r_vec += [(a + b * x) % L for a, b in zip(p["r0"], p["r1"])]
-    t_x %= L
-    tau_x %= L
-    mu %= L
+    t_x = (t_x + (fd if kind == "t_x" else 0)) % L           # (the sent values: the witness l_vec, r_vec keeps the true inner product)
+    tau_x = (tau_x + (fd if kind == "tau" else 0)) % L
+    mu = (mu + (fd if kind == "mu" else 0)) % L
     tr.append_scalar(b"t_x", t_x)
     tr.append_scalar(b"t_x_blinding", tau_x)
     tr.append_scalar(b"e_blinding", mu)
@@ -676,42 +727,71 @@ def range_prove(values, blindings, n, tape: Tape, label=b"", commit_values=None,
     Q = w * BASEPOINT
     y_inv = inv(y)
     H_factors = [pow(y_inv, i, L) for i in range(n * m)]
-    ipp = _ipp_create(tr, Q, H_factors, list(G), list(H), l_vec, r_vec)
+    us = []
+    ipp_forge = dict(f, point=_forge_point(f, G, H), d=fd) if kind in ("L_k", "R_k", "a", "b") else None
+    ipp = _ipp_create(tr, Q, H_factors, list(G), list(H), l_vec, r_vec, forge=ipp_forge, us=us)
+    if info is not None:
+        info.update(x=x, w=w, u=us, A=A_c, S=S_c, T1=T1_c, T2=T2_c)
     return A_c + S_c + T1_c + T2_c + scalar_bytes(t_x) + scalar_bytes(tau_x) + scalar_bytes(mu) + ipp
 
 
-def _ipp_create(tr, Q, H_factors, G, H, a, b):
-    """InnerProductProof::create (G_factors all one)."""
+def _ipp_create(tr, Q, H_factors, G, H, a, b, forge=None, us=None):
+    """InnerProductProof::create (G_factors all one).  forge (range_prove): L_k / R_k of round k moved by d * point before it is
+    absorbed, or the final a / b sent as value + d; us (a list) receives the round challenges."""
     nn = len(G)
     tr.innerproduct_domain_sep(nn)
     H = [f * h for f, h in zip(H_factors, H)]  # first-round H' = y^-i H_i, folded in eagerly (same group elements)
     out = b""
+    kind = forge["kind"] if forge else None
+    rnd = 0
     while nn != 1:
         nn //= 2
         a_L, a_R, b_L, b_R = a[:nn], a[nn:], b[:nn], b[nn:]
         G_L, G_R, H_L, H_R = G[:nn], G[nn:], H[:nn], H[nn:]
         c_L, c_R = _ip(a_L, b_R), _ip(a_R, b_L)
-        Lp = (_msm(a_L, G_R) + _msm(b_R, H_L) + c_L * Q).compress()
-        Rp = (_msm(a_R, G_L) + _msm(b_L, H_R) + c_R * Q).compress()
+        Lpt = _msm(a_L, G_R) + _msm(b_R, H_L) + c_L * Q
+        Rpt = _msm(a_R, G_L) + _msm(b_L, H_R) + c_R * Q
+        if kind == "L_k" and forge["k"] == rnd:
+            Lpt = Lpt + forge["d"] * forge["point"]
+        if kind == "R_k" and forge["k"] == rnd:
+            Rpt = Rpt + forge["d"] * forge["point"]
+        Lp, Rp = Lpt.compress(), Rpt.compress()
         out += Lp + Rp
         tr.append_point(b"L", Lp)
         tr.append_point(b"R", Rp)
         u = tr.challenge_scalar(b"u")
+        if us is not None:
+            us.append(u)
         u_inv = inv(u)
         a = [(x * u + u_inv * yv) % L for x, yv in zip(a_L, a_R)]
         b = [(x * u_inv + u * yv) % L for x, yv in zip(b_L, b_R)]
         G = [u_inv * gl + u * gr for gl, gr in zip(G_L, G_R)]
         H = [u * hl + u_inv * hr for hl, hr in zip(H_L, H_R)]
-    return out + scalar_bytes(a[0]) + scalar_bytes(b[0])
+        rnd += 1
+    fa = a[0] + (forge["d"] if kind == "a" else 0)
+    fb = b[0] + (forge["d"] if kind == "b" else 0)
+    return out + scalar_bytes(fa) + scalar_bytes(fb)
 
 
 def range_proof_size(n, m):
     return 32 * (9 + 2 * (n * m).bit_length() - 2)
 
 
-def range_verify(proof: bytes, commitments, n, c=None, label=b""):
+def range_verify(proof: bytes, commitments, n, c=None, label=b"", info=None):
     """RangeProof::from_bytes + verify_multiple (src/range/mod.rs:83-119).  `c` = the verifier's random
-    batching scalar (thread_rng in the crate); any non-zero value gives the same verdict for honest proofs."""
+    batching scalar (thread_rng in the crate); any non-zero value gives the same verdict for honest proofs.
+
+    The check is one point sum, acc(c) = acc_P + c * acc_t = identity: acc_P is the inner-product equation (P) and acc_t the
+    polynomial equation (t) that the verifier weighs by c.  With info (a dict) the call returns (verdict, residual of P, residual
+    of t), both compressed -- acc(0) and acc(1) - acc(0); an honest proof leaves the identity (32 zero bytes) in both -- and info
+    receives the challenges y, z, x, w, u and c.  A proof that does not parse returns (False, None, None)."""
+    if info is not None:
+        ok = _range_verify(proof, commitments, n, c, label, info)
+        return (ok, info.get("res_P"), info.get("res_t"))
+    return _range_verify(proof, commitments, n, c, label, None)
+
+
+def _range_verify(proof, commitments, n, c, label, info):
     m = len(commitments)
     if len(proof) % 32 or len(proof) < 7 * 32:
         return False
@@ -775,10 +855,6 @@ def range_verify(proof: bytes, commitments, n, c=None, label=b""):
     sum_2 = (2**n - 1) % L
     sum_z = sum(pow(z, j, L) for j in range(m)) % L
     delta = ((z - zz) * sum_y - z * zz % L * sum_2 % L * sum_z) % L
-    scal = [1, x, c * x % L, c * x % L * x % L] + u_sq + u_inv_sq
-    scal += [(pow(z, j, L) * c % L * zz) % L for j in range(m)]
-    acc = _msm(scal, pts)
-    acc = acc + ((-mu - c * tau_x) % L) * B_BLINDING + ((w * (t_x - a * b) + c * (delta - t_x)) % L) * BASEPOINT
     g_s = [(-z - a * s[i]) % L for i in range(nm)]
     h_s = []
     exp_y_inv = 1
@@ -786,8 +862,20 @@ def range_verify(proof: bytes, commitments, n, c=None, label=b""):
         z_and_2 = pow(z, i // n, L) * pow(2, i % n, L) % L
         h_s.append((z + exp_y_inv * (zz * z_and_2 - b * s[nm - 1 - i])) % L)
         exp_y_inv = exp_y_inv * y_inv % L
-    acc = acc + _msm(g_s, G) + _msm(h_s, H)
-    return acc == IDENTITY
+    if info is None:
+        scal = [1, x, c * x % L, c * x % L * x % L] + u_sq + u_inv_sq
+        scal += [(pow(z, j, L) * c % L * zz) % L for j in range(m)]
+        acc = _msm(scal, pts)
+        acc = acc + ((-mu - c * tau_x) % L) * B_BLINDING + ((w * (t_x - a * b) + c * (delta - t_x)) % L) * BASEPOINT
+        acc = acc + _msm(g_s, G) + _msm(h_s, H)
+        return acc == IDENTITY
+    # the same sum split by the power of c: acc_P (c^0) and acc_t (c^1)
+    acc_P = _msm([1, x, 0, 0] + u_sq + u_inv_sq + [0] * m, pts)
+    acc_P = acc_P + ((-mu) % L) * B_BLINDING + (w * (t_x - a * b) % L) * BASEPOINT + _msm(g_s, G) + _msm(h_s, H)
+    acc_t = _msm([0, 0, x, x * x % L] + [0] * (2 * lg) + [pow(z, j, L) * zz % L for j in range(m)], pts)
+    acc_t = acc_t + ((-tau_x) % L) * B_BLINDING + ((delta - t_x) % L) * BASEPOINT
+    info.update(y=y, z=z, x=x, w=w, u=us, c=c, res_P=acc_P.compress(), res_t=acc_t.compress())
+    return acc_P + c * acc_t == IDENTITY
 
 
 # ----------------------------------------------------------------------------------------------------------
