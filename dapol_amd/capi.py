@@ -121,6 +121,14 @@ _SIG = {
     "dapol_shared_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),
     "dapol_prove_entities_shared": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
                                                      _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dapol_shared_compact_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),
+    "dapol_shared_expand": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t,
+                                             ctypes.c_size_t, ctypes.c_size_t, _P]),
+    "dapol_shared_compress": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_size_t, _P]),
+    "dapol_prove_entities_shared_compact": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
+                                                             _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P]),
+    "dapol_verify_entities_compact": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, ctypes.c_int32,
+                                                       ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P]),
     "dapol_reprove_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
     "dapol_reprove_entities_shared": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P,
                                                        _P, _P]),
@@ -132,6 +140,7 @@ _SIG = {
     "dapol_proof_store_fetch": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
     "dapol_proof_store_read": (ctypes.c_int32, [_P, ctypes.c_size_t, ctypes.c_size_t, _P, _P, _P, _P]),
     "dapol_proof_store_verify": (ctypes.c_int32, [_P, _P, _P]),
+    "dapol_proof_store_read_compact": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P]),
     "dapol_workload_create": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_create_shard": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_build": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(WorkloadStats)]),
@@ -456,6 +465,24 @@ class Context:
                                                 policy, aggregation_factor, n_bits, _ptr(rp), rp.shape[0], _ptr(seed), _ptr(ok), ctypes.byref(unique)))
         return ok, int(unique.value)
 
+    def verify_entities_compact(self, height, leaf_idx, leaf_C, leaf_H, path_C, path_H, root_C, root_H, policy, aggregation_factor, n_bits, compact,
+                                verify_seed=None):
+        """dapol_verify_entities_compact: verify_entities' verdicts over shared_expand(compact), every distinct sub-proof uploaded once.
+        Returns (ok, unique): unique = range proofs actually checked."""
+        leaf_idx = _u64(leaf_idx)
+        b = leaf_idx.shape[0]
+        lC, lH = _u8(leaf_C, b, 32), _u8(leaf_H, b, self.hb)
+        pC, pH = _u8(path_C).reshape(-1, 32), _u8(path_H).reshape(-1, self.hb)
+        cp = _u8(compact).reshape(-1)
+        rC, rH = _u8(np.frombuffer(root_C, np.uint8)), _u8(np.frombuffer(root_H, np.uint8))
+        seed = _u8(np.frombuffer(verify_seed, np.uint8)) if verify_seed is not None else None   # None: the library draws one from the OS
+        ok, unique = np.zeros(b, np.uint8), ctypes.c_uint64(0)
+        if pH.shape[0] != pC.shape[0]:
+            return ok, 0
+        _chk(lib().dapol_verify_entities_compact(self.h, height, b, _ptr(leaf_idx), _ptr(lC), _ptr(lH), pC.shape[0], _ptr(pC), _ptr(pH), _ptr(rC), _ptr(rH),
+                                                 policy, aggregation_factor, n_bits, _ptr(cp), cp.shape[0], _ptr(seed), _ptr(ok), ctypes.byref(unique)))
+        return ok, int(unique.value)
+
     def verify_batch(self, height, leaf_idx, leaf_C, leaf_H, sib_C, sib_H, root_C, root_H, policy, aggregation_factor, n_bits, range_proofs,
                      verify_seed=None):
         """DapolProof::verify_batch: one proof covering k leaves."""
@@ -512,6 +539,46 @@ def shared_plan(height, leaf_idx, policy, aggregation_factor):
     _chk(lib().dapol_shared_plan(height, leaf_idx.shape[0], _ptr(leaf_idx), policy, aggregation_factor, _ptr(n_sub), ctypes.byref(tot), ctypes.byref(per)))
     b = leaf_idx.shape[0]
     return n_sub[:per.value // b if b else 0], int(tot.value), int(per.value)
+
+
+def shared_compact_plan(height, leaf_idx, policy, aggregation_factor, n_bits):
+    """dapol_shared_compact_plan (host-only): (sub_off [n_sub + 1] byte offsets of each sub-proof's list of distinct proofs,
+    ref [n_sub][b] = the proof of its list that each row uses, the compact buffer's length)."""
+    leaf_idx = _u64(leaf_idx)
+    b = leaf_idx.shape[0]
+    n_sub = max(height, 0) + 1                                   # a plan has at most height + 1 sub-proofs
+    sub_off, ref, length = np.zeros(n_sub + 1, np.uint64), np.zeros(max(n_sub * b, 1), np.uint32), ctypes.c_uint64(0)
+    _chk(lib().dapol_shared_compact_plan(height, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(sub_off), _ptr(ref), ctypes.byref(length)))
+    n = len(shared_plan(height, [0], policy, aggregation_factor)[0])          # the plan's size (leaf 0 exists at every height)
+    return sub_off[:n + 1], ref[:n * b].reshape(n, b), int(length.value)
+
+
+def shared_expand(height, leaf_idx, policy, aggregation_factor, n_bits, compact, first=0, count=None):
+    """dapol_shared_expand (host-only): rows [first, first + count) (count None: to the end) of the compact buffer as per-entity
+    blobs [count][entity bytes]."""
+    leaf_idx = _u64(leaf_idx)
+    b = leaf_idx.shape[0]
+    count = b - first if count is None else count
+    compact = _u8(compact).reshape(-1)
+    es = lib().dapol_entity_proof_size(height, policy, aggregation_factor, n_bits)
+    out = np.zeros((max(count, 0), max(es, 1)), np.uint8)
+    _chk(lib().dapol_shared_expand(height, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(compact), compact.shape[0], first, count, _ptr(out)))
+    return out
+
+
+def shared_compress(height, leaf_idx, policy, aggregation_factor, n_bits, blobs):
+    """dapol_shared_compress (host-only): the compact buffer of expanded blobs [b][entity bytes] (the first row of every run)."""
+    leaf_idx = _u64(leaf_idx)
+    b = leaf_idx.shape[0]
+    blobs = _u8(blobs).reshape(-1)
+    length = ctypes.c_uint64(0)
+    _chk(lib().dapol_shared_compact_plan(height, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, None, None, ctypes.byref(length)))
+    es = lib().dapol_entity_proof_size(height, policy, aggregation_factor, n_bits)
+    if blobs.shape[0] != b * es:
+        raise DapolError(8, "the blobs must hold dapol_entity_proof_size bytes per entity")
+    out = np.zeros(length.value, np.uint8)
+    _chk(lib().dapol_shared_compress(height, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(blobs), _ptr(out), out.shape[0], ctypes.byref(length)))
+    return out[:length.value]
 
 
 def reprove_plan(height, leaf_idx, edited_idx, policy, aggregation_factor, has_old=None):
@@ -811,6 +878,25 @@ class Tree:
                                                _ptr(uC), _ptr(uH), _ptr(uv), _ptr(ur), _ptr(C), _ptr(H), _ptr(out), ctypes.byref(unique)))
         return C, H, out, int(unique.value)
 
+    def prove_entities_shared_compact(self, leaf_idx, policy, aggregation_factor, n_bits, nonce_seed, upper=None):
+        """dapol_prove_entities_shared_compact: prove_entities_shared with the range output in the compact form (every distinct sub-proof
+        once; shared_expand gives the blobs).  Returns (path_C, path_H, compact, range proofs actually computed)."""
+        leaf_idx = _u64(leaf_idx)
+        nu = 0 if upper is None else len(upper[2])
+        b, h = leaf_idx.shape[0], self.height + nu
+        C, H = np.zeros((b, h, 32), np.uint8), np.zeros((b, h, self.ctx.hb), np.uint8)
+        length = ctypes.c_uint64(0)
+        if lib().dapol_shared_compact_plan(h, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, None, None, ctypes.byref(length)) != 0:
+            length = ctypes.c_uint64(0)                              # (the call below refuses with its own code and message)
+        out = np.zeros(max(length.value, 1), np.uint8)
+        seed = _u8(np.frombuffer(nonce_seed, np.uint8))
+        uC, uH, uv, ur = (None,) * 4 if not nu else (_u8(upper[0], nu, 32), _u8(upper[1], nu, 32), _u64(upper[2]), _u8(upper[3], nu, 32))
+        unique = ctypes.c_uint64(0)
+        _chk(lib().dapol_prove_entities_shared_compact(self.ctx.h, self.h, b, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(seed), nu,
+                                                       _ptr(uC), _ptr(uH), _ptr(uv), _ptr(ur), _ptr(C), _ptr(H), _ptr(out), length.value,
+                                                       ctypes.byref(length), ctypes.byref(unique)))
+        return C, H, out[:length.value], int(unique.value)
+
     def reprove_entities_shared(self, leaf_idx, old_leaf_idx, old_path_C, old_blobs, policy, aggregation_factor, n_bits, nonce_seed):
         """dapol_reprove_entities_shared: prove_entities_shared's outputs for the tree as it is now, proving only the sub-proofs whose
         sibling commitments differ from old_path_C; the others keep the bytes of old_blobs.  old_leaf_idx (strictly increasing) names
@@ -848,6 +934,7 @@ class ProofStore:
         _chk(lib().dapol_proof_store_create(tree.ctx.h, tree.h, policy, aggregation_factor, n_bits, _ptr(seed), ctypes.byref(self.h)))
         self.H = tree.height
         self.entity_bytes = int(lib().dapol_proof_store_entity_bytes(self.h))
+        self.policy, self.aggregation_factor, self.n_bits = policy, aggregation_factor, n_bits
 
     def close(self):
         if self.h:
@@ -896,6 +983,19 @@ class ProofStore:
         C, H, out = self._out(max(count, 0))
         _chk(lib().dapol_proof_store_read(self.h, first, count, _ptr(idx), _ptr(C), _ptr(H), _ptr(out)))
         return idx, C, H, out
+
+    def read_compact(self):
+        """dapol_proof_store_read_compact: (leaf_idx, compact) -- the range proofs of all rows in the compact layout of their own leaf
+        indexes (every distinct sub-proof once; shared_expand gives the blobs)."""
+        n = self.rows
+        idx = np.zeros(n, np.uint64)
+        if n:
+            _chk(lib().dapol_proof_store_read(self.h, 0, n, _ptr(idx), None, None, None))
+        length = ctypes.c_uint64(0)
+        _chk(lib().dapol_shared_compact_plan(self.H, n, _ptr(idx), self.policy, self.aggregation_factor, self.n_bits, None, None, ctypes.byref(length)))
+        out = np.zeros(max(length.value, 1), np.uint8)
+        _chk(lib().dapol_proof_store_read_compact(self.h, _ptr(out), length.value, ctypes.byref(length)))
+        return idx, out[:length.value]
 
     def verify(self, verify_seed=None):
         """verify_entities' verdicts for every row against the tree as it is now; only the verdict bytes leave the device."""

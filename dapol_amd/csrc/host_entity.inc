@@ -60,7 +60,8 @@ static int32_t entity_shape(const dapol_ctx* ctx, const dapol_tree* tree, bool p
 }
 
 // The device side of a per-entity proving call (the prover's counterpart of VerifyCallDev, host_verify.inc): open() uploads, paths()
-// gathers the siblings, the entry point proves into out, download() copies back.
+// gathers the siblings, the entry point proves into out, download() copies back.  with_out = false: the call has no [b][es] buffer
+// (the compact shared call, host_shared.inc, whose range output is the distinct proofs alone) and download() copies the paths only.
 struct EntityProveCall {
     dapol_ctx* ctx = nullptr;
     dapol_tree* tree = nullptr;
@@ -69,12 +70,12 @@ struct EntityProveCall {
     DevBuf<uint32_t> seed, pathC, pathH, pr, pos, out;    // nonce seed (null in tape mode); siblings [b][H]; range proofs [b][es / 4]
     UpperDev up;
     int32_t open(dapol_ctx* ctx_, dapol_tree* tree_, const EntityShape& S, size_t b_, const uint64_t* leaf_idx, const uint8_t* seed32_or_null, int n_upper,
-                 const uint8_t* up_C32, const uint8_t* up_H32, const uint64_t* up_v, const uint8_t* up_r32) {
+                 const uint8_t* up_C32, const uint8_t* up_H32, const uint64_t* up_v, const uint8_t* up_r32, bool with_out = true) {
         ctx = ctx_; tree = tree_; b = b_; tot = b * (size_t)S.H; es = S.es;
         HIPCHK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         HIPCHK(idx.alloc(b)); HIPCHK(seed.alloc(seed32_or_null ? 8 : 0)); HIPCHK(pathC.alloc(tot * 8)); HIPCHK(pathH.alloc(tot * (size_t)ctx_hw(ctx)));
-        HIPCHK(out.alloc(b * es / 4)); HIPCHK(pv.alloc(tot)); HIPCHK(pr.alloc(tot * 8)); HIPCHK(pos.alloc(b));
+        HIPCHK(out.alloc(with_out ? b * es / 4 : 0)); HIPCHK(pv.alloc(tot)); HIPCHK(pr.alloc(tot * 8)); HIPCHK(pos.alloc(b));
         HIPCHK(hipMemcpyAsync(idx.p, leaf_idx, b * 8, hipMemcpyHostToDevice, st));
         if (seed32_or_null) HIPCHK(hipMemcpyAsync(seed.p, seed32_or_null, 32, hipMemcpyHostToDevice, st));
         return up.upload(st, n_upper, up_C32, up_H32, up_v, up_r32);
@@ -83,7 +84,7 @@ struct EntityProveCall {
     int32_t download(uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out) {
         if (path_C32) HIPCHK(hipMemcpy(path_C32, pathC.p, tot * 32, hipMemcpyDeviceToHost));
         if (path_H32) HIPCHK(hipMemcpy(path_H32, pathH.p, tot * ctx_hash_bytes(ctx), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(range_out, out.p, b * es, hipMemcpyDeviceToHost));
+        if (out.p) HIPCHK(hipMemcpy(range_out, out.p, b * es, hipMemcpyDeviceToHost));
         return DAPOL_OK;
     }
 };

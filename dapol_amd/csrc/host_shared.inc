@@ -77,19 +77,29 @@ static int32_t shared_plan_dev_build(const std::vector<SubProof>& plan, size_t b
     return DAPOL_OK;
 }
 
-// The shared counterpart of prove_policy_device: pv / pr / pC are the gathered [b][H] siblings, d_idx the b ascending leaf indexes.
-static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t b, int H, const uint64_t* pv, const uint32_t* pr,
-                                          const uint32_t* pC, int n_bits, const uint32_t* d_seed, const uint64_t* d_idx, uint32_t* d_range,
-                                          uint64_t* unique_out) {
-    hipStream_t st = ctx->stream;
+// What the shared call holds before its scatter: the plan as the kernels take it, the ranks, and the distinct proofs group after
+// group -- which is the compact layout of shared_compact_plan.inc as it lies (words * 4 bytes).
+struct SharedProved {
     SharedPlanDev P;
+    DevBuf<uint32_t> flag, rank, proofs;
+    size_t words = 0;
+    uint64_t unique = 0;
+};
+// Everything of the shared call up to the scatter: heads, scan, gather, one call of the range prover per group.  pv / pr / pC are
+// the gathered [b][H] siblings, d_idx the b ascending leaf indexes.  expect_heads (may be null): the head count that the host worked
+// out from the indexes; another count on the device is an internal error, returned before anything is proven.
+static int32_t prove_policy_shared_compact_device(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t b, int H, const uint64_t* pv, const uint32_t* pr,
+                                                  const uint32_t* pC, int n_bits, const uint32_t* d_seed, const uint64_t* d_idx, const uint64_t* expect_heads,
+                                                  SharedProved& R) {
+    hipStream_t st = ctx->stream;
+    SharedPlanDev& P = R.P;
+    DevBuf<uint32_t>&flag = R.flag, &rank = R.rank, &proofs = R.proofs;
     int32_t rc = shared_plan_dev_build(plan, b, H, n_bits, P);
     if (rc) return rc;
     // heads and ranks: rank[s][e] = heads up to and including (s, e) in plan order, so rank - 1 is the compact row of the statement
     // that (s, e) belongs to -- its own if it is a head, its predecessors' otherwise; the last element (a closing zero flag) counts
     // all heads.  Row 0 of every sub-proof is a head: a group's first compact row is rank[s0][0] - 1.
     const size_t nf = (size_t)P.n_sub * b + 1;
-    DevBuf<uint32_t> flag, rank;
     HIPCHK(flag.alloc(nf)); HIPCHK(rank.alloc(nf));
     hipLaunchKernelGGL(k_shared_heads, dim3(nblk(nf, 256)), dim3(256), 0, st, P, b, d_idx, flag.p);
     LAUNCH_CHECK();
@@ -102,7 +112,8 @@ static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubP
     }
     HIPCHK(hipStreamSynchronize(st));
     for (uint32_t gi = 0; gi < P.n_groups; gi++) g_first[gi]--;
-    if (unique_out) *unique_out = g_first[P.n_groups];
+    R.unique = g_first[P.n_groups];
+    if (expect_heads && *expect_heads != R.unique) return fail(DAPOL_ERR_HIP, "internal error: the device counts other heads than the host's layout");
     // compact gather: the head rows' parties, group after group
     size_t parties = 0, words = 0;
     std::vector<size_t> p_off(P.n_groups);
@@ -111,8 +122,9 @@ static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubP
         p_off[gi] = parties; P.g[gi].word_off = words;
         parties += U * P.g[gi].m; words += U * (size_t)P.g[gi].pieces * 4;
     }
+    R.words = words;
     DevBuf<uint64_t> vals, stream;
-    DevBuf<uint32_t> blind, Vc, proofs;
+    DevBuf<uint32_t> blind, Vc;
     HIPCHK(vals.alloc(parties)); HIPCHK(blind.alloc(parties * 8)); HIPCHK(Vc.alloc(parties * 8)); HIPCHK(stream.alloc(g_first[P.n_groups]));
     HIPCHK(proofs.alloc(words));
     const uint32_t* Bb_comp = ctx->gens_comp.p + (size_t)ctx->tv.row_Bb(0) * 8;
@@ -130,8 +142,19 @@ static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubP
                                 stream.p + g_first[gi], 0, nullptr, proofs.p + G.word_off, nullptr);
         if (rc) return rc;
     }
+    return DAPOL_OK;
+}
+// The shared counterpart of prove_policy_device: the compact proofs, then the scatter into the [b] blobs of d_range.
+static int32_t prove_policy_shared_device(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t b, int H, const uint64_t* pv, const uint32_t* pr,
+                                          const uint32_t* pC, int n_bits, const uint32_t* d_seed, const uint64_t* d_idx, uint32_t* d_range,
+                                          uint64_t* unique_out) {
+    hipStream_t st = ctx->stream;
+    SharedProved R;
+    int32_t rc = prove_policy_shared_compact_device(ctx, plan, b, H, pv, pr, pC, n_bits, d_seed, d_idx, nullptr, R);
+    if (rc) return rc;
+    if (unique_out) *unique_out = R.unique;
     // scatter: every (entity, sub-proof) copies its proof from its compact row
-    hipLaunchKernelGGL(k_shared_scatter, dim3(nblk(b * (size_t)P.entity_pieces, 256)), dim3(256), 0, st, P, b, rank.p, (const uint4*)proofs.p, (uint4*)d_range);
+    hipLaunchKernelGGL(k_shared_scatter, dim3(nblk(b * (size_t)R.P.entity_pieces, 256)), dim3(256), 0, st, R.P, b, R.rank.p, (const uint4*)R.proofs.p, (uint4*)d_range);
     LAUNCH_CHECK();
     HIPCHK(hipStreamSynchronize(st));
     return DAPOL_OK;
@@ -155,5 +178,95 @@ int32_t dapol_prove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b, 
         if (rc || (rc = call.download(path_C32, path_H32, range_out))) return rc;
     }
     if (unique_subproofs_out) *unique_subproofs_out = unique;
+    return DAPOL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the compact form
+// dapol_shared_compact_plan / _expand / _compress: host-only (shared_compact_plan.inc).  The refusals of dapol_shared_plan plus n_bits.
+static int32_t scompact_host_plan(int32_t height, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                                  bool check_range, SCompactPlan& P) {
+    if (b && !leaf_idx) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    if (height < 0 || height > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
+    std::vector<SubProof> plan;
+    if (!policy_plan(policy, height, aggregation_factor, plan)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad policy / aggregation_factor");
+    if (dapol_range_proof_size(n_bits, 1) == 0) return fail(DAPOL_ERR_INVALID_ARGUMENT, "bad n_bits");
+    if (!strictly_increasing(b, leaf_idx) || (check_range && b && height < 64 && (leaf_idx[b - 1] >> height) != 0))
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "leaf indexes must be strictly increasing and below 2^height");
+    if (scompact_plan_build(plan, height, n_bits, g_wire.siblings_leaf_first != 0, P))
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "the plan has too many sub-proofs or runs of equal-sized sub-proofs");
+    if (!vshared_call_fits(b, plan.size()))
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "too many sub-proofs in one call (entities x (plan size + 1) must stay below 2^32)");
+    return DAPOL_OK;
+}
+int32_t dapol_shared_compact_plan(int32_t height, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                                  uint64_t* sub_off, uint32_t* ref, uint64_t* compact_len) {
+    WIRE_SCOPE();
+    SCompactPlan P;
+    int32_t rc = scompact_host_plan(height, b, leaf_idx, policy, aggregation_factor, n_bits, true, P);
+    if (rc) return rc;
+    const uint64_t len = scompact_layout(P, b, leaf_idx, sub_off, ref);
+    if (compact_len) *compact_len = len;
+    return DAPOL_OK;
+}
+int32_t dapol_shared_expand(int32_t height, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                            const uint8_t* compact, size_t compact_len, size_t first, size_t count, uint8_t* range_out) {
+    WIRE_SCOPE();
+    SCompactPlan P;
+    int32_t rc = scompact_host_plan(height, b, leaf_idx, policy, aggregation_factor, n_bits, true, P);
+    if (rc) return rc;
+    if (first > b || count > b - first) return fail(DAPOL_ERR_INVALID_ARGUMENT, "first + count exceeds the rows");
+    if (scompact_layout(P, b, leaf_idx, nullptr, nullptr) != (uint64_t)compact_len)
+        return fail(DAPOL_ERR_INVALID_ARGUMENT, "compact_len is not the length of the compact layout of these leaves");
+    if (count && (!compact || !range_out)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    if (count) scompact_expand(P, b, leaf_idx, compact, first, count, range_out);
+    return DAPOL_OK;
+}
+int32_t dapol_shared_compress(int32_t height, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                              const uint8_t* range_blobs, uint8_t* compact_out, size_t compact_cap, uint64_t* compact_len_out) {
+    WIRE_SCOPE();
+    SCompactPlan P;
+    int32_t rc = scompact_host_plan(height, b, leaf_idx, policy, aggregation_factor, n_bits, true, P);
+    if (rc) return rc;
+    const uint64_t len = scompact_layout(P, b, leaf_idx, nullptr, nullptr);
+    if (len > (uint64_t)compact_cap) return fail(DAPOL_ERR_INVALID_ARGUMENT, "compact_cap is below the length of the compact layout");
+    if (b && (!range_blobs || !compact_out)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    if (b) scompact_compress(P, b, leaf_idx, range_blobs, compact_out);
+    if (compact_len_out) *compact_len_out = len;
+    return DAPOL_OK;
+}
+
+// dapol_prove_entities_shared without its scatter: the distinct proofs leave the device as they lie.  No [b][entity bytes] buffer
+// exists on the device in this call.
+int32_t dapol_prove_entities_shared_compact(dapol_ctx* ctx, dapol_tree* tree, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor,
+                                            int32_t n_bits, const uint8_t nonce_seed32[32], int32_t n_upper, const uint8_t* up_C32, const uint8_t* up_H32,
+                                            const uint64_t* up_v, const uint8_t* up_r32, uint8_t* path_C32, uint8_t* path_H32, uint8_t* compact_out,
+                                            size_t compact_cap, uint64_t* compact_len_out, uint64_t* unique_subproofs_out) {
+    WIRE_SCOPE();
+    EntityShape S;
+    int32_t rc = entity_shape(ctx, tree, nonce_seed32 && (!b || (leaf_idx && compact_out)), "null or out-of-range argument", n_upper, policy, aggregation_factor,
+                              n_bits, true, true, S);
+    if (rc) return rc;
+    if (!strictly_increasing(b, leaf_idx)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "leaf indexes must be strictly increasing");
+    // the layout from the indexes alone, before anything is queued (an index outside the tree is the unknown leaf of paths() below)
+    SCompactPlan P;
+    if ((rc = scompact_host_plan(S.H, b, leaf_idx, policy, aggregation_factor, n_bits, false, P))) return rc;
+    std::vector<uint64_t> sub_off(P.V.n_sub + 1);
+    const uint64_t len = scompact_layout(P, b, leaf_idx, sub_off.data(), nullptr);
+    if (len > (uint64_t)compact_cap) return fail(DAPOL_ERR_INVALID_ARGUMENT, "compact_cap is below the length of the compact layout");
+    uint64_t heads = 0;
+    for (uint32_t s = 0; s < P.V.n_sub; s++) heads += (sub_off[s + 1] - sub_off[s]) / ((uint64_t)P.V.pieces[s] * 16);
+    if (b) {
+        EntityProveCall call;
+        if ((rc = call.open(ctx, tree, S, b, leaf_idx, nonce_seed32, n_upper, up_C32, up_H32, up_v, up_r32, false)) || (rc = call.paths())) return rc;
+        SharedProved R;
+        rc = prove_policy_shared_compact_device(ctx, S.plan, b, S.H, call.pv.p, call.pr.p, call.pathC.p, n_bits, call.seed.p, call.idx.p, &heads, R);
+        if (rc) return rc;
+        if ((uint64_t)R.words * 4 != len) return fail(DAPOL_ERR_HIP, "internal error: the device's compact buffer has another length than the host's layout");
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if ((rc = call.download(path_C32, path_H32, nullptr))) return rc;
+        HIPCHK(hipMemcpy(compact_out, R.proofs.p, (size_t)len, hipMemcpyDeviceToHost));
+    }
+    if (compact_len_out) *compact_len_out = len;
+    if (unique_subproofs_out) *unique_subproofs_out = heads;
     return DAPOL_OK;
 }

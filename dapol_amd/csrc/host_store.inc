@@ -270,3 +270,49 @@ int32_t dapol_proof_store_verify(dapol_proof_store* s, const uint8_t verify_seed
     HIPCHK(hipMemcpy(ok, dok, b, hipMemcpyDeviceToHost));
     return DAPOL_OK;
 }
+
+// Every stored row in the compact layout of the stored leaf indexes (shared_compact_plan.inc): the key heads over the store's own
+// indexes, a scan, one gather out of the blobs into a staging buffer of exactly the compact length, one copy back.
+int32_t dapol_proof_store_read_compact(dapol_proof_store* s, uint8_t* compact_out, size_t compact_cap, uint64_t* compact_len_out) {
+    WIRE_SCOPE();
+    int32_t rc = store_usable(s);
+    if (rc) return rc;
+    const size_t b = s->rows;
+    uint64_t len = 0;
+    if (b) {
+        dapol_ctx* ctx = s->ctx;
+        HIPCHK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        SharedPlanDev P;
+        if ((rc = shared_plan_dev_build(s->S.plan, b, s->S.H, s->n_bits, P))) return rc;
+        const size_t nf = (size_t)P.n_sub * b + 1;
+        DevBuf<uint32_t> flag, rank, stage;
+        HIPCHK(flag.alloc(nf)); HIPCHK(rank.alloc(nf));
+        hipLaunchKernelGGL(k_shared_heads, dim3(nblk(nf, 256)), dim3(256), 0, st, P, b, s->idx.p, flag.p);
+        LAUNCH_CHECK();
+        if ((rc = inclusive_scan_u32(st, flag.p, rank.p, nf))) return rc;
+        std::vector<uint32_t> g_first(P.n_groups + 1);           // compact row at which each group starts; the last one: all of them
+        for (uint32_t gi = 0; gi <= P.n_groups; gi++) {
+            const size_t at = gi < P.n_groups ? (size_t)P.g[gi].s0 * b : nf - 1;
+            HIPCHK(hipMemcpyAsync(&g_first[gi], rank.p + at, 4, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        for (uint32_t gi = 0; gi < P.n_groups; gi++) g_first[gi]--;
+        size_t words = 0;
+        for (uint32_t gi = 0; gi < P.n_groups; gi++) {
+            P.g[gi].word_off = words;
+            words += (size_t)(g_first[gi + 1] - g_first[gi]) * (size_t)P.g[gi].pieces * 4;
+        }
+        len = (uint64_t)words * 4;
+        if (len > (uint64_t)compact_cap) return fail(DAPOL_ERR_INVALID_ARGUMENT, "compact_cap is below the length of the compact layout");
+        if (!compact_out) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+        HIPCHK(stage.alloc(words));
+        hipLaunchKernelGGL(k_store_compact, dim3(nblk(b * (size_t)P.entity_pieces, 256)), dim3(256), 0, st, P, b, flag.p, rank.p, (const uint4*)s->range.p,
+                           (uint4*)stage.p);
+        LAUNCH_CHECK();
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(compact_out, stage.p, (size_t)len, hipMemcpyDeviceToHost));
+    }
+    if (compact_len_out) *compact_len_out = len;
+    return DAPOL_OK;
+}

@@ -493,18 +493,20 @@ struct VerifyCallDev {
     DevBuf<uint8_t> arena;
     uint32_t *dPC = nullptr, *dR = nullptr, *dseed = nullptr, *dV = nullptr;
     uint8_t *dok = nullptr, *dsub = nullptr, *dpath = nullptr;
+    uint64_t* dl = nullptr;              // the uploaded leaf indexes
     bool side_paths = false;
 };
-static int32_t verify_upload_and_paths(dapol_ctx* ctx, ForkGuard& fg, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* leaf_C32,
-                                       const uint8_t* leaf_H32, const uint8_t* path_C32, const uint8_t* path_H32, const uint8_t root_C32[32],
-                                       const uint8_t root_H32[32], size_t es, const uint8_t* range_proofs, const uint8_t verify_seed32[32],
-                                       size_t v_parties, VerifyCallDev& D) {
+// (range_bytes: the bytes of range_proofs as a whole -- b blobs, or the compact buffer of host_verify_compact.inc)
+static int32_t verify_upload_bytes_and_paths(dapol_ctx* ctx, ForkGuard& fg, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* leaf_C32,
+                                             const uint8_t* leaf_H32, const uint8_t* path_C32, const uint8_t* path_H32, const uint8_t root_C32[32],
+                                             const uint8_t root_H32[32], size_t range_bytes, const uint8_t* range_proofs, const uint8_t verify_seed32[32],
+                                             size_t v_parties, VerifyCallDev& D) {
     hipStream_t st = ctx->stream;
     const size_t tot = b * (size_t)height;
     // One device arena for the call's inputs and verdict bytes; small calls also stage the nine host arrays into ONE upload
     // (a pageable-memory copy costs ~20 us of latency however small: 0.24 ms of a 2.2 ms single-proof check).
     const size_t hb = ctx_hash_bytes(ctx);                        // leaf_H32 / path_H32 / root_H32: hb bytes per node (32, or 64 for Blake2b)
-    const size_t sizes[12] = {b * 8, b * 32, b * hb, tot * 32 + 32, tot * hb + 64, b * es, 32 + 64, 32, b, b, b, b * v_parties * 32};
+    const size_t sizes[12] = {b * 8, b * 32, b * hb, tot * 32 + 32, tot * hb + 64, range_bytes, 32 + 64, 32, b, b, b, b * v_parties * 32};
     size_t offs[12], total = 0;
     for (int i = 0; i < 12; i++) { offs[i] = total; total += align_up(sizes[i], 256); }
     HIPCHK(D.arena.alloc(total));
@@ -515,7 +517,7 @@ static int32_t verify_upload_and_paths(dapol_ctx* ctx, ForkGuard& fg, int32_t he
     uint8_t *dok = base + offs[8], *dsub = base + offs[9], *dpath = base + offs[10];
     uint32_t* dV = (uint32_t*)(base + offs[11]);
     const void* src[8] = {leaf_idx, leaf_C32, leaf_H32, path_C32, path_H32, range_proofs, nullptr, verify_seed32};
-    const size_t src_bytes[8] = {b * 8, b * 32, b * hb, tot * 32, tot * hb, b * es, 32 + hb, 32};
+    const size_t src_bytes[8] = {b * 8, b * 32, b * hb, tot * 32, tot * hb, range_bytes, 32 + hb, 32};
     const size_t in_end = offs[8];                                  // the inputs are the arena's head
     if (in_end <= ((size_t)1 << 20)) {
         std::vector<uint8_t> stage(in_end, 0);
@@ -555,8 +557,16 @@ static int32_t verify_upload_and_paths(dapol_ctx* ctx, ForkGuard& fg, int32_t he
     HIPCHK(hipMemsetAsync(dok, 1, b, st));
     D.dPC = dPC; D.dR = dR; D.dseed = dseed; D.dV = dV;
     D.dok = dok; D.dsub = dsub; D.dpath = dpath;
+    D.dl = dl;
     D.side_paths = side_paths;
     return DAPOL_OK;
+}
+static int32_t verify_upload_and_paths(dapol_ctx* ctx, ForkGuard& fg, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* leaf_C32,
+                                       const uint8_t* leaf_H32, const uint8_t* path_C32, const uint8_t* path_H32, const uint8_t root_C32[32],
+                                       const uint8_t root_H32[32], size_t es, const uint8_t* range_proofs, const uint8_t verify_seed32[32],
+                                       size_t v_parties, VerifyCallDev& D) {
+    return verify_upload_bytes_and_paths(ctx, fg, height, b, leaf_idx, leaf_C32, leaf_H32, path_C32, path_H32, root_C32, root_H32, b * es, range_proofs,
+                                         verify_seed32, v_parties, D);
 }
 
 // DapolProof::verify (src/proof/mod.rs:41-47, :89-95) for b single-leaf proofs: Merkle re-merge, then R::verify over the

@@ -7,10 +7,12 @@
 //                   writes every piece);
 //   k_store_find    a lane per query: its row, or none;
 //   k_store_fetch   the rows of the queries gathered into a staging buffer, zero for "none";
-//   k_store_leaves  the leaves' own commitments and hashes from level 0 of the tree (dapol_proof_store_verify).
+//   k_store_leaves  the leaves' own commitments and hashes from level 0 of the tree (dapol_proof_store_verify);
+//   k_store_compact the key-head rows' sub-proofs gathered out of the blobs into the compact layout (dapol_proof_store_read_compact).
 // No LDS, no atomics.  All index arithmetic is in size_t: 2^22 rows of 24 KB are more than 2^32 pieces.  The searches are store_plan.inc's.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "kernels_shared.h"
 #include "store_plan.inc"
 
 namespace dapol {
@@ -82,6 +84,25 @@ __global__ __launch_bounds__(256) void k_store_leaves(size_t b, size_t hq, const
     const size_t p = pos[e];
     if (q < 2) leaf_C[e * 2 + q] = C0[p * 2 + q];
     else leaf_H[e * hq + (q - 2)] = H0[p * hq + (q - 2)];
+}
+
+// dapol_proof_store_read_compact: k_shared_scatter the other way round.  Piece q of row e's blob belongs to sub-proof s of group G; where
+// (s, e) is a key head (flag, k_shared_heads over the stored indexes) it goes to compact row rank[s][e] - rank[s0][0] of the group's
+// slice of the staging buffer, which has exactly the compact length.  The other rows' pieces are copies and are not read.
+__global__ __launch_bounds__(256) void k_store_compact(SharedPlanDev P, size_t b, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank,
+                                                       const uint4* __restrict__ blobs, uint4* __restrict__ compact) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= b * (size_t)P.entity_pieces) return;
+    const size_t e = t / P.entity_pieces;
+    const uint32_t q = (uint32_t)(t - e * P.entity_pieces);
+    uint32_t gi = 0;
+    while (gi + 1 < P.n_groups && q >= P.g[gi + 1].q0) gi++;
+    const SharedGroup G = P.g[gi];
+    const uint32_t j = (q - G.q0) / G.pieces, piece = (q - G.q0) - j * G.pieces;
+    const size_t f = (size_t)(G.s0 + j) * b + e;
+    if (!flag[f]) return;
+    const size_t row = (size_t)(rank[f] - rank[(size_t)G.s0 * b]);
+    compact[G.word_off / 4 + row * G.pieces + piece] = blobs[t];
 }
 
 }  // namespace dapol

@@ -576,6 +576,79 @@ class Dapol {
                                                                        const std::vector<DapolProof>& proofs, const Bytes32& verify_seed) {
         return verify_many_shared(ctx, root, leaves, proofs, verify_seed.data());
     }
+    // The COMPACT form of generate_proofs_shared (dapol_prove_entities_shared_compact): the Merkle paths per leaf and every distinct
+    // sub-proof once -- what leaves the GPU and what verify_proofs_compact takes.  expand() cuts the proofs of single leaves out.
+    struct CompactProofs {
+        std::vector<uint64_t> leaves;                    // strictly increasing
+        std::vector<std::vector<DapolProofNode>> merkle_siblings;       // [leaf][height]
+        std::vector<uint8_t> compact;                    // the layout of dapol_shared_compact_plan over `leaves`
+        uint64_t unique = 0;                             // range proofs actually computed
+        Policy policy = Policy::Padding;
+        size_t aggregation_factor = 0;
+        int n_bits = 64, height = 0;
+        // proofs [first, first + count) as generate_proofs_shared returns them (count = 1: one user's proof)
+        std::vector<DapolProof> expand(size_t first, size_t count) const {
+            const size_t es = dapol_entity_proof_size(height, (int)policy, (int)aggregation_factor, n_bits);
+            std::vector<uint8_t> R(count * es + 1);
+            check(dapol_shared_expand(height, leaves.size(), leaves.data(), (int)policy, (int)aggregation_factor, n_bits, compact.data(), compact.size(), first, count,
+                                      R.data()));
+            std::vector<DapolProof> out(count);
+            for (size_t i = 0; i < count; i++) {
+                out[i].leaf_index = leaves[first + i];
+                out[i].merkle_siblings = merkle_siblings[first + i];
+                out[i].range_proofs.assign(R.begin() + i * es, R.begin() + (i + 1) * es);
+                out[i].policy = policy; out[i].aggregation_factor = aggregation_factor; out[i].n_bits = n_bits; out[i].height = height;
+            }
+            return out;
+        }
+        std::vector<DapolProof> expand() const { return expand(0, leaves.size()); }
+    };
+    std::optional<CompactProofs> generate_proofs_compact(const std::vector<uint64_t>& leaves, const Bytes32& nonce_seed, int n_bits = 64) const {
+        const size_t b = leaves.size(), h = (size_t)height_;
+        uint64_t len = 0;
+        check(dapol_shared_compact_plan(height_, b, leaves.data(), (int)policy_, (int)aggregation_factor_, n_bits, nullptr, nullptr, &len));
+        CompactProofs out;
+        std::vector<uint8_t> C(b * h * 32 + 1), H(b * h * 32 + 1);
+        out.compact.resize((size_t)len + 1);                                 // never pass a null data pointer
+        int32_t rc = dapol_prove_entities_shared_compact(ctx_->get(), tree_.get(), b, leaves.data(), (int)policy_, (int)aggregation_factor_, n_bits, nonce_seed.data(),
+                                                         0, nullptr, nullptr, nullptr, nullptr, C.data(), H.data(), out.compact.data(), (size_t)len, &len, &out.unique);
+        if (rc == DAPOL_ERR_UNKNOWN_LEAF) return std::nullopt;
+        check(rc);
+        out.compact.resize((size_t)len);
+        out.leaves = leaves;
+        out.merkle_siblings.assign(b, std::vector<DapolProofNode>(h));
+        for (size_t e = 0; e < b; e++)
+            for (size_t s = 0; s < h; s++) {
+                std::memcpy(out.merkle_siblings[e][s].com.data(), &C[(e * h + s) * 32], 32);
+                std::memcpy(out.merkle_siblings[e][s].hash.data(), &H[(e * h + s) * 32], 32);
+            }
+        out.policy = policy_; out.aggregation_factor = aggregation_factor_; out.n_bits = n_bits; out.height = height_;
+        return out;
+    }
+    // dapol_verify_entities_compact: the verdicts DapolProof::verify gives for proofs.expand() one by one, with every distinct sub-proof
+    // uploaded and checked once, and the number of range proofs actually checked.  proofs.leaves[i] is checked against leaves[i].
+    static std::pair<std::vector<bool>, uint64_t> verify_proofs_compact(const Context& ctx, const DapolProofNode& root, const std::vector<DapolProofNode>& leaves,
+                                                                        const CompactProofs& proofs, const uint8_t* verify_seed32 = nullptr) {
+        const size_t b = proofs.leaves.size();
+        if (leaves.size() != b || proofs.merkle_siblings.size() != b) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        std::vector<bool> out(b, false);
+        if (b == 0) return {out, 0};
+        std::vector<uint8_t> lC(b * 32), lH(b * 32), C, H, R(proofs.compact);
+        for (size_t e = 0; e < b; e++) {
+            std::memcpy(&lC[e * 32], leaves[e].com.data(), 32);
+            std::memcpy(&lH[e * 32], leaves[e].hash.data(), 32);
+            for (auto& s : proofs.merkle_siblings[e]) { C.insert(C.end(), s.com.begin(), s.com.end()); H.insert(H.end(), s.hash.begin(), s.hash.end()); }
+        }
+        const size_t n_nodes = C.size() / 32, r_len = R.size();
+        C.push_back(0); H.push_back(0); R.push_back(0);                     // never pass a null data pointer
+        std::vector<uint8_t> ok(b, 0);
+        uint64_t unique = 0;
+        check(dapol_verify_entities_compact(ctx.get(), proofs.height, b, proofs.leaves.data(), lC.data(), lH.data(), n_nodes, C.data(), H.data(), root.com.data(),
+                                            root.hash.data(), (int)proofs.policy, (int)proofs.aggregation_factor, proofs.n_bits, R.data(), r_len, verify_seed32,
+                                            ok.data(), &unique));
+        for (size_t e = 0; e < b; e++) out[e] = ok[e] != 0;
+        return {out, unique};
+    }
   private:
     static std::pair<std::vector<bool>, uint64_t> verify_many_shared(const Context& ctx, const DapolProofNode& root, const std::vector<DapolProofNode>& leaves,
                                                                      const std::vector<DapolProof>& proofs, const uint8_t* verify_seed) {

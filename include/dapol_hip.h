@@ -361,6 +361,45 @@ int32_t dapol_prove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b, 
                                     const uint8_t* up_C32, const uint8_t* up_H32, const uint64_t* up_v, const uint8_t* up_r32,
                                     uint8_t* path_C32, uint8_t* path_H32, uint8_t* range_out, uint64_t* unique_subproofs_out);
 
+/* COMPACT shared proofs: every distinct sub-proof of a call leaves the prover and enters the verifier ONCE.  The index that such a
+ * form needs costs nothing: the rows ascend, so which proof row e of sub-proof s uses is a function of leaf_idx and the plan alone.
+ *   Definition.  For strictly increasing leaf_idx below 2^height and the policy's plan in blob order, sub-proof s has n_unique[s]
+ * distinct subtree keys S (above) among the rows.  The COMPACT BUFFER is, for s = 0 .. n_sub - 1 in plan order, the n_unique[s]
+ * proofs of sub-proof s in ascending key order, each dapol_range_proof_size(n_bits, m_s) bytes.  ref[s][e] = (distinct keys of s among
+ * rows 0 .. e) - 1 is the proof of that list that row e uses; sub_off[s] is the byte offset of the list of s and sub_off[n_sub] the
+ * total length.  A run of the plan's sub-proofs of equal m is contiguous: one [rows][proof bytes] batch.  It is the order in which
+ * dapol_prove_entities_shared holds the proofs before it expands them.  Honours the sibling order of dapol_wire_config.
+ *   Host-only (no context, no GPU), refusals as dapol_shared_plan plus a bad n_bits (DAPOL_ERR_INVALID_ARGUMENT):
+ *   dapol_shared_compact_plan: sub_off [n_sub + 1] (may be NULL), ref [n_sub][b] (may be NULL), *compact_len (may be NULL).
+ *   dapol_shared_expand: the per-entity blobs (dapol_entity_proof_size layout) of rows [first, first + count) into range_out; count = 1
+ * cuts one user's proof out.  A compact_len that is not the layout's length, or first + count > b -> DAPOL_ERR_INVALID_ARGUMENT with
+ * nothing written.
+ *   dapol_shared_compress: the inverse for a caller who holds expanded blobs [b][entity bytes]: the bytes of the first row of every
+ * run of equal keys; the other rows are not read.  compact_cap below the layout's length -> DAPOL_ERR_INVALID_ARGUMENT, nothing written.
+ *   dapol_prove_entities_shared_compact: arguments, refusals and path outputs as dapol_prove_entities_shared (n_upper included); the
+ * range output is the compact buffer: compact_out [compact_cap], *compact_len_out (may be NULL) its length, which is
+ * dapol_shared_compact_plan's for (tree height + n_upper, leaf_idx).  The length is computed on the host before anything is queued; a
+ * compact_cap below it -> DAPOL_ERR_INVALID_ARGUMENT with nothing written.  dapol_shared_expand of the output equals
+ * dapol_prove_entities_shared's blobs byte for byte.  No [b][entity bytes] buffer is allocated on the device.
+ *   When to use it (tools/bench_shared_compact.py, DESIGN.md section 4.4, profiles/shared_compact_2e18_h30.json: 2^18 random leaves
+ * at height 30, 64-bit proofs, one MI355X, whole calls): what the call saves is the scatter, the download of every copy and the
+ * [b][entity bytes] device buffer.  The bytes follow the count of distinct proofs: x1.19 fewer at padding / 16 (2.706 -> 2.666 s,
+ * -1.5 %), x1.14 at splitting / 24 (2.807 -> 2.803 s: inside the shared call's 1.2 % spread, a MISS), x2.36 at padding / 0 (2.249 ->
+ * 2.122 s, -5.7 %).  Proving dominates these calls, so use it for the memory and for a consumer that takes the compact form
+ * (dapol_verify_entities_compact), not for prover time.  Do not use it where dapol_shared_plan reports nothing to share (padding /
+ * height: 4.490 -> 4.489 s, no gain): dapol_prove_entities' blobs are the same bytes there. */
+int32_t dapol_shared_compact_plan(int32_t height, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                                  uint64_t* sub_off, uint32_t* ref, uint64_t* compact_len);
+int32_t dapol_shared_expand(int32_t height, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                            const uint8_t* compact, size_t compact_len, size_t first, size_t count, uint8_t* range_out);
+int32_t dapol_shared_compress(int32_t height, size_t b, const uint64_t* leaf_idx, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                              const uint8_t* range_blobs, uint8_t* compact_out, size_t compact_cap, uint64_t* compact_len_out);
+int32_t dapol_prove_entities_shared_compact(dapol_ctx* ctx, dapol_tree* tree, size_t b, const uint64_t* leaf_idx, int32_t policy,
+                                            int32_t aggregation_factor, int32_t n_bits, const uint8_t nonce_seed32[32], int32_t n_upper,
+                                            const uint8_t* up_C32, const uint8_t* up_H32, const uint64_t* up_v, const uint8_t* up_r32,
+                                            uint8_t* path_C32, uint8_t* path_H32, uint8_t* compact_out, size_t compact_cap,
+                                            uint64_t* compact_len_out, uint64_t* unique_subproofs_out);
+
 /* RE-PROVING after an edit of the tree (dapol_tree_update / _insert / _remove): a sub-proof {start, count, m} is a statement about
  * `count` sibling commitments, a sibling changes only when an edited leaf lies below it, and the shared prover's nonce key is bound
  * to the seed, S, (n, m) and those commitments -- so an unchanged statement has unchanged bytes and a changed one gets fresh nonces.
@@ -444,6 +483,13 @@ int32_t dapol_reprove_entities_shared(dapol_ctx* ctx, dapol_tree* tree, size_t b
  * passes an edited leaf fails (all but a lone edited leaf's own row: its edit lies below none of its own siblings), which is the point
  * of the check.  Only the verdict bytes cross the bus.  verify_seed32 = NULL draws one, as elsewhere.  A stored leaf that the
  * tree no longer holds -> DAPOL_ERR_UNKNOWN_LEAF, nothing written.
+ *   dapol_proof_store_read_compact: the range proofs of ALL stored rows in the compact layout of their own leaf indexes ("COMPACT
+ * shared proofs" above: dapol_shared_compact_plan over dapol_proof_store_read's leaf indexes gives the length and the index;
+ * dapol_shared_expand gives the blobs back).  The first row of every run of equal subtree keys is gathered on the device into a
+ * staging buffer of exactly that length and copied back once; the store itself stays as it is.  compact_cap below the length ->
+ * DAPOL_ERR_INVALID_ARGUMENT with nothing written; an empty store gives length 0.  Refresh + read of everything against refresh +
+ * read_compact (same file): 0.187 -> 0.079 s at padding / 0, where the leg is all bus; within 1 % at padding / 16 and splitting / 24,
+ * where the refresh is proving.
  *   When to use it (tools/bench_proof_store.py): whenever proofs are served after edits and the caller does not
  * need every blob back after every edit. */
 typedef struct dapol_proof_store dapol_proof_store;
@@ -459,6 +505,7 @@ int32_t dapol_proof_store_fetch(dapol_proof_store* store, size_t k, const uint64
 int32_t dapol_proof_store_read(dapol_proof_store* store, size_t first, size_t count, uint64_t* leaf_idx_out, uint8_t* path_C32,
                                uint8_t* path_H32, uint8_t* range_out);
 int32_t dapol_proof_store_verify(dapol_proof_store* store, const uint8_t verify_seed32[32], uint8_t* ok);
+int32_t dapol_proof_store_read_compact(dapol_proof_store* store, uint8_t* compact_out, size_t compact_cap, uint64_t* compact_len_out);
 
 /* Serializable for RangeProofPadding / RangeProofSplitting (src/range/padding.rs:38-69, src/range/splitting.rs:36-84):
  * the range-proof blob of ONE entity as written by dapol_prove_entities <-> R::serialize() bytes
@@ -592,6 +639,30 @@ int32_t dapol_verify_entities_shared(dapol_ctx* ctx, int32_t height, size_t b, c
                                      size_t n_path_nodes, const uint8_t* path_C32, const uint8_t* path_H32, const uint8_t root_C32[32],
                                      const uint8_t root_H32[32], int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint8_t* range_proofs,
                                      size_t range_proofs_len, const uint8_t verify_seed32[32], uint8_t* ok, uint64_t* unique_subproofs_out);
+
+/* dapol_verify_entities_compact: the verifier over the COMPACT form (above, "COMPACT shared proofs"): every distinct sub-proof is
+ * uploaded once.  Arguments as dapol_verify_entities_shared with (compact, compact_len) in place of (range_proofs, range_proofs_len).
+ * leaf_idx must be strictly increasing (DAPOL_ERR_INVALID_ARGUMENT otherwise); a wrong n_path_nodes, or a compact_len that is not the
+ * layout's length for these leaves, gives ok = 0, *unique = 0 and DAPOL_OK.
+ *   Definition.  ok[] equals what dapol_verify_entities returns for the same leaves, paths and root with dapol_shared_expand(compact)
+ * as the blobs -- for every input, tampered ones included.  Nothing but bytes is trusted: row e of sub-proof s = {start, count, m} is a
+ * HEAD iff e = 0, or its subtree key differs from row e - 1's, or any of the `count` sibling commitments the sub-proof covers differs
+ * from row e - 1's.  A head is checked once, against its own row's commitments, with the proof at compact row ref[s][e] of s; the
+ * rows behind it up to the next head inherit its verdict (they name the same proof bytes over the same commitments).
+ * *unique_subproofs_out = the number of heads; on honest input that is dapol_shared_plan's total.  A corrupted row therefore fails
+ * alone and does not take honest rows of the same subtree with it: the verdict vector is the per-proof one, through the same random
+ * linear combination with its eight-way split as everywhere in the verifier.
+ *   Limits as dapol_verify_entities_shared; calls with b x plan size <= 64 expand on the host, forward to dapol_verify_entities and
+ * report *unique = b x plan size (the same test-only override moves that limit).
+ *   When to use it (tools/bench_shared_compact.py, DESIGN.md section 4.6, profiles/shared_compact_2e18_h30.json: 2^18 random leaves at
+ * height 30, 64-bit proofs, one MI355X, whole calls against dapol_verify_entities fed the expansion): padding / 16 0.398 -> 0.336 s
+ * (x1.18), splitting / 24 0.243 -> 0.213 s (x1.14), padding / 0 0.756 -> 0.341 s (x2.22); the time follows the number of range proofs
+ * checked, the upload (14-16 % of a call there) shrinks by the byte ratio.  Where nothing is shared (padding / height) 0.088 -> 0.089 s:
+ * either call serves. */
+int32_t dapol_verify_entities_compact(dapol_ctx* ctx, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* leaf_C32, const uint8_t* leaf_H32,
+                                      size_t n_path_nodes, const uint8_t* path_C32, const uint8_t* path_H32, const uint8_t root_C32[32],
+                                      const uint8_t root_H32[32], int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint8_t* compact,
+                                      size_t compact_len, const uint8_t verify_seed32[32], uint8_t* ok, uint64_t* unique_subproofs_out);
 
 /* Multi-GPU: one process per GPU, rank g owning the top-level subtree with index prefix g (dapol_tree_build_shard /
  * dapol_workload_create_shard).  The reference has no communication (single process, single thread); the sharded path has
