@@ -87,6 +87,7 @@ _SIG = {
     "dapol_tree_update": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P]),
     "dapol_tree_remove": (ctypes.c_int32, [_P, ctypes.c_size_t, _P]),
     "dapol_tree_insert": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P]),
+    "dapol_tree_apply": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, _P, _P, _P]),
     "dapol_tree_derive_leaves": (ctypes.c_int32, [_P, ctypes.c_int32, _P, ctypes.c_size_t, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dapol_tree_insert_liabilities": (ctypes.c_int32, [_P, ctypes.c_int32, _P, ctypes.c_size_t, ctypes.c_size_t, _P, _P, _P, _P, _P, _P]),
     "dapol_tree_last_update_path": (ctypes.c_int32, [_P, _P]),
@@ -773,6 +774,19 @@ class Tree:
         leaf_idx, v, r32 = _u64(leaf_idx), _u64(v), _u8(r32)
         _chk(lib().dapol_tree_insert(self.h, leaf_idx.shape[0], _ptr(leaf_idx), _ptr(v), _ptr(r32)))
 
+    def apply(self, remove_idx, put_idx, put_v, put_r32):
+        """dapol_tree_apply: removals and puts as one edit, all or nothing -- the leaves at remove_idx go, a put replaces the leaf at
+        its index or adds one.  An index twice among the puts, or both removed and put, a removal that is not a leaf, or a result with
+        no leaf is an error with the tree unchanged.  Returns put_was_new: per put, whether it added a leaf."""
+        remove_idx, put_idx, put_v = _u64(remove_idx), _u64(put_idx), _u64(put_v)
+        n_put = put_idx.shape[0]
+        put_r32 = _u8(put_r32, n_put, 32)
+        if put_v.shape[0] != n_put:
+            raise DapolError(8, "put_idx and put_v differ in length")
+        was_new = np.zeros(max(n_put, 1), np.uint8)
+        _chk(lib().dapol_tree_apply(self.h, remove_idx.shape[0], _ptr(remove_idx), n_put, _ptr(put_idx), _ptr(put_v), _ptr(put_r32), _ptr(was_new)))
+        return was_new[:n_put].astype(bool)
+
     def derive_leaves(self, liabilities, audit_seed, digest=DIGEST_BLAKE3):
         """dapol_tree_derive_leaves: build_leaf_nodes for liabilities [(internal_id bytes, external_id bytes, value)] that JOIN this
         tree -- an index that is a leaf now is taken.  Nothing is written; the result is build_leaf_nodes' dict for the batch."""
@@ -793,8 +807,9 @@ class Tree:
         return by_e
 
     def last_update_path(self):
-        """What the last update, insert or removal did: 0 = rebuilt the tree, 1 = replaced in place, 2 = inserted in place (disjoint
-        chains), 3 = both, 4 = removed in place, 5 = inserted in place by insert()'s general path."""
+        """What the last update, insert, removal or apply did: 0 = rebuilt the tree, 1 = replaced in place, 2 = inserted in place
+        (disjoint chains), 3 = both, 4 = removed in place, 5 = inserted in place by insert()'s general path, 6 = applied in place by
+        apply()."""
         p = ctypes.c_int32(-1)
         _chk(lib().dapol_tree_last_update_path(self.h, ctypes.byref(p)))
         return int(p.value)

@@ -57,7 +57,7 @@ struct dapol_tree_owned : dapol_tree {
     // (ping-pong; the arena region it came from is simply left behind).  cur = which of the two holds the level now (-1: still in the arena).
     struct LevelAlt { DevBuf<uint8_t> buf[2]; size_t cap[2] = {0, 0}; int cur = -1; };
     std::vector<LevelAlt> alt;
-    int last_update_path = 0;    // what the last dapol_tree_update / _remove did (dapol_tree_last_update_path)
+    int last_update_path = 0;    // what the last dapol_tree_update / _insert / _remove / _apply did (dapol_tree_last_update_path)
     bool holds_ctx = false;      // API-created trees keep their context alive (workload trees live inside a workload that does)
 };
 

@@ -919,6 +919,101 @@ __global__ __launch_bounds__(64) void k_tree_edit_merge(int digest, LevelView cu
 // chain tops sit at different levels, so the deltas of one ancestor would have to be gathered across chains; a merge reads what
 // is already there (children of the level below, the padding records of R2) and needs no bookkeeping between chains.
 
+// ------------------------------------------------------------------------------------- mixed edit in place
+// dapol_tree_apply: removals, new leaves and replacements as ONE edit.  The host plans the forest of touched nodes once
+// (plan_apply, tree_edit_plan.inc): which die, which are born, which survive; then every level up to the highest that changes is
+// rewritten once with both lists, and every alive touched node is made once, bottom-up.
+//   A0  k_tree_apply_plan     per edited index: lower bound, existence and has_pad of its ancestor at every level (a search down to
+//                             the first ancestor that exists, parent pointers from there)
+//   A1  k_tree_relayout       per level below the highest that changes: survivors move by (born before) - (dead before)
+//   A2  k_tree_apply_struct   per alive touched node, and per untouched sibling S of a node that died or was born: has_pad as it is
+//                             afterwards; a born node also gets idx and parent
+//   A3  k_tree_ins_leaves     per put, new or replacing: the leaf's node at its new position, its extended point in its slot
+//   A4  k_tree_edit_pad<1>    per padding node the plan lists (the old tree did not hold that position's record)
+//   A5  k_tree_apply_merge    per level: every alive touched node = the parent of an anchor child and the anchor's other child
+// The insert's rule holds: a point this call has produced is never decoded again.  Either child of a merge comes from a slot (a
+// touched node or put leaf), a pad slot, or is decoded (an untouched real node, an old padding record) -- so a survivor above a dead
+// chain top, whose children are the untouched S and S's new padding node, pays one decoding where the removal's merge pays two.
+// Compiler report, gfx950: profiles/tree_apply_kernel_resources.txt.
+struct TreeApplyPlan {
+    size_t k;
+    int height;
+    const uint64_t* idx;       // [k] sorted, distinct: the removed and the put indexes together
+    uint32_t* pos;             // [k][height + 1]: old-layout lower bound of idx >> t (the node's position where it exists)
+    uint8_t* flag;             // [k][height + 1]: bit 0 = the node exists, bit 1 = its has_pad
+};
+// A0.  Nothing of the tree is written.
+__global__ __launch_bounds__(64) void k_tree_apply_plan(const LevelView* views, TreeApplyPlan P) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= P.k) return;
+    const uint64_t x = P.idx[j];
+    const size_t stride = (size_t)P.height + 1;
+    uint32_t* pos = P.pos + j * stride;
+    uint8_t* flag = P.flag + j * stride;
+    bool found = false;
+    size_t p = 0;
+    for (int t = 0; t <= P.height; t++) {
+        const LevelView L = views[t];
+        if (!found) {
+            const uint64_t want = t < 64 ? x >> t : 0;
+            p = lower_bound_u64(L.idx, L.n, want);
+            found = p < L.n && L.idx[p] == want;
+        }
+        pos[t] = (uint32_t)p;
+        flag[t] = !found ? 0 : (t < P.height && L.has_pad[p]) ? 3 : 1;
+        if (found && t < P.height) p = L.parent[p];
+    }
+}
+struct TreeApplyStruct {
+    size_t n;
+    const uint32_t *lvl, *pos, *parent, *flag, *idx_lo, *idx_hi;   // [n]: plan_apply's s_*
+};
+// A2
+__global__ __launch_bounds__(64) void k_tree_apply_struct(const LevelView* views, TreeApplyStruct G) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= G.n) return;
+    const LevelView L = views[G.lvl[i]];
+    const size_t d = G.pos[i];
+    const uint32_t f = G.flag[i];
+    if (f & 1u) {
+        L.idx[d] = (uint64_t)G.idx_lo[i] | ((uint64_t)G.idx_hi[i] << 32);
+        L.parent[d] = G.parent[i];
+    }
+    L.has_pad[d] = (uint8_t)((f >> 1) & 1u);
+}
+// A5, one level: five words per node of nxt to make from its children in cur (new layout): the node's position | the position of its
+// anchor child | the node's slot | the anchor's slot, or 0xffffffff = decode it | the other child (the anchor's padding record or
+// real neighbour, as k_tree_merge pairs them): a slot of cur's half, 0x80000000 | pad slot, or 0xffffffff = decode it.  The node's
+// point is left in its slot.
+template <int DX>
+__global__ __launch_bounds__(64) void k_tree_apply_merge(int digest, LevelView cur, LevelView nxt, size_t n, const uint32_t* e, const int32_t* ext_cur,
+                                                         int32_t* ext_nxt, const int32_t* pad_ext) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* rec = e + 5 * i;
+    const size_t p = rec[0], c = rec[1];
+    const bool left = (cur.idx[c] & 1ull) == 0;
+    uint32_t cA[8], hA[8], rA[8], cB[8], hB[8], rB[8];
+    const uint64_t vA = cur.v[c];
+    uint64_t vB;
+    ld8(cA, cur.C + c * 8); ld8(hA, cur.H + c * 8); ld8(rA, cur.r + c * 8);
+    load_other_child(cB, hB, rB, &vB, cur, c, left);
+    ge_p3 pA, pB, pp;
+    const uint32_t anchor = rec[3], other = rec[4];
+    if (anchor == 0xffffffffu) (void)ge_decompress(pA, cA);
+    else ld_p3(pA, ext_cur + (size_t)anchor * 40);
+    if (other == 0xffffffffu) (void)ge_decompress(pB, cB);
+    else if (other & 0x80000000u) ld_p3(pB, pad_ext + (size_t)(other & 0x7fffffffu) * 40);
+    else ld_p3(pB, ext_cur + (size_t)other * 40);
+    uint32_t rp[8], cp[8], hp[8];
+    merge_parent<DX>(pp, rp, cp, hp, digest, left, pA, pB, rA, rB, cA, cB, hA, hB);
+    nxt.v[p] = vA + vB;                            // u64 wrap == release-mode Rust (node.rs:72)
+    st8(nxt.r + p * 8, rp);
+    st8(nxt.C + p * 8, cp);
+    st8(nxt.H + p * 8, hp);
+    st_p3(ext_nxt + (size_t)rec[2] * 40, pp);
+}
+
 // ------------------------------------------------------------------------------------- small trees, by phases
 // k_tree_merge makes a level in one pass, which is right for millions of nodes (one trip through HBM) and wrong for a tree of a
 // few thousand (the reference's `build` criterion group, benches/dapol.rs:24-57; dapol_tree_update): a level is then ONE lane's

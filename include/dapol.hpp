@@ -478,6 +478,51 @@ class Dapol {
         remove(idx);
         for (auto& id : ids) id_to_idx_map_.erase(id);
     }
+    // A mixed change set as ONE edit (dapol_tree_apply; all or nothing): the liabilities at `remove` go, a put replaces the liability
+    // at its index or adds one, and the tree equals a build over the resulting leaves with the same seed.  Returns, per put, whether
+    // it added a leaf.  Throws with nothing applied: DapolError(DAPOL_ERR_INVALID_ARGUMENT) for an index twice among the puts, an
+    // index both removed and put, or a result with no leaf; DapolError(DAPOL_ERR_UNKNOWN_LEAF) for a removal that is not a leaf.
+    // Where three calls to remove / insert / update would leave the first ones applied when a later one is refused, this leaves none.
+    std::vector<bool> apply(const std::vector<uint64_t>& remove, const std::vector<uint64_t>& put_idx, const std::vector<uint64_t>& values,
+                            const std::vector<Bytes32>& blindings) {
+        if (put_idx.size() != values.size() || put_idx.size() != blindings.size()) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        if (remove.empty() && put_idx.empty()) return {};
+        if (!tree_) throw DapolError(remove.empty() ? DAPOL_ERR_INVALID_ARGUMENT : DAPOL_ERR_UNKNOWN_LEAF);      // (a blank Dapol: build or insert)
+        std::vector<uint8_t> was_new(put_idx.size() + 1);
+        check(dapol_tree_apply(tree_.get(), remove.size(), remove.data(), put_idx.size(), put_idx.data(), values.data(),
+                               blindings.empty() ? nullptr : blindings[0].data(), was_new.data()));
+        return std::vector<bool>(was_new.begin(), was_new.end() - 1);
+    }
+    // The same by internal id, for a Dapol made by create: the liabilities of remove_ids go and `liabilities` join in one edit.  The new
+    // indexes are derived as insert_liabilities derives them (dapol_tree_derive_leaves: the tree's current leaves count as taken, those
+    // that go in this very call included).  An unknown id to remove throws DapolError(DAPOL_ERR_UNKNOWN_LEAF); a new internal id that is
+    // in id_to_idx_map() already -- also one that is being removed -- or given twice throws DapolError(DAPOL_ERR_DUPLICATED_INTERNAL_ID);
+    // both before the library is called.  id_to_idx_map() changes only when the library call has succeeded.
+    void apply_liabilities(const std::vector<LiabilityId>& remove_ids, const std::vector<Liability>& liabilities) {
+        if (!created_ || !tree_) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        std::vector<uint64_t> gone;
+        for (auto& id : remove_ids) {
+            auto it = id_to_idx_map_.find(id);
+            if (it == id_to_idx_map_.end()) throw DapolError(DAPOL_ERR_UNKNOWN_LEAF);
+            gone.push_back(it->second);
+        }
+        const size_t k = liabilities.size();
+        std::map<LiabilityId, uint64_t> fresh;
+        for (auto& l : liabilities)
+            if (id_to_idx_map_.count(l.internal_id) || !fresh.emplace(l.internal_id, 0).second) throw DapolError(DAPOL_ERR_DUPLICATED_INTERNAL_ID);
+        if (gone.empty() && k == 0) return;
+        std::vector<uint64_t> idx(k), v(k), by_entity(k);
+        std::vector<Bytes32> r(k);
+        std::vector<uint32_t> order(k);
+        if (k) {
+            const Packed L(liabilities);
+            check(dapol_tree_derive_leaves(tree_.get(), digest_, audit_seed_.data(), audit_seed_.size(), k, L.iid.data(), L.ioff.data(), L.eid.data(),
+                                           L.eoff.data(), L.vals.data(), idx.data(), v.data(), r[0].data(), order.data(), by_entity.data()));
+        }
+        check(dapol_tree_apply(tree_.get(), gone.size(), gone.data(), k, idx.data(), v.data(), k ? r[0].data() : nullptr, nullptr));
+        for (auto& id : remove_ids) id_to_idx_map_.erase(id);
+        for (size_t i = 0; i < k; i++) id_to_idx_map_[liabilities[i].internal_id] = by_entity[i];
+    }
     // Dapol::root_raw / Dapol::root (mod.rs:134-141)
     DapolNode root_raw() const {
         DapolNode n;

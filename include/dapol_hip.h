@@ -260,9 +260,30 @@ int32_t dapol_tree_derive_leaves(dapol_tree* tree, int32_t digest_id, const uint
 int32_t dapol_tree_insert_liabilities(dapol_tree* tree, int32_t digest_id, const uint8_t* audit_seed, size_t audit_seed_len, size_t k,
                                       const uint8_t* internal_ids, const uint32_t* internal_off, const uint8_t* external_ids,
                                       const uint32_t* external_off, const uint64_t* values, uint64_t* idx_by_entity);
-/* What the last dapol_tree_update / dapol_tree_insert / dapol_tree_remove on this tree did: 0 = rebuilt, 1 = replaced existing leaves
- * in place, 2 = inserted new leaves in place (disjoint chains), 3 = both, 4 = removed leaves in place, 5 = inserted new leaves in place
- * by dapol_tree_insert's general path (diagnostics; the tree is the same whichever path ran). */
+/* A mixed change set as ONE edit: afterwards the leaf set is (old leaves - the leaves at remove_idx) + the puts.  A put at an index that
+ * is a leaf replaces that liability, a put at any other index adds a leaf; put_was_new[n_put] (may be NULL; written on success only)
+ * says which it was, in input order.  The tree then equals dapol_tree_build (dapol_tree_build_shard) over that leaf set with the
+ * tree's pad seed bit for bit, at every level -- node counts, padding records, has_pad and parent pointers included -- whichever path
+ * ran.  Leaves keep their blinding as given (bit 255 cleared, possibly >= l), value sums wrap, as in dapol_tree_insert.
+ * ALL OR NOTHING -- every refusal is decided before the first write and leaves the tree unchanged and usable (dapol_last_error says
+ * which rule was broken), in this order: an index twice in put_idx, or an index in both remove_idx and put_idx (a replacement is a put
+ * alone) -> DAPOL_ERR_INVALID_ARGUMENT; a remove_idx entry that is not a leaf (also one outside the tree or outside a shard's prefix)
+ * -> DAPOL_ERR_UNKNOWN_LEAF; a put outside the tree or outside a shard's prefix -> the code dapol_tree_update returns for that index;
+ * a result with no leaf left -> DAPOL_ERR_INVALID_ARGUMENT.  A duplicate in remove_idx removes its leaf once; n_remove = n_put = 0
+ * does nothing.  Refused like dapol_tree_update: trees built from a padding tape, workload trees, trees marked invalid.
+ * Batches with height >= 1, every index in range, n_remove + n_put within update_incremental_max (dapol_options), at most 65,536, at
+ * most an eighth of the leaves plus one, and at most 2^31 leaves afterwards go IN PLACE on the device: one planning launch, every
+ * level up to the highest that changes rewritten once with what it gains and what it loses, every touched node made once.  A HIP
+ * failure between the first and the last write of that path marks the tree invalid, as for dapol_tree_update.  Any other batch
+ * rebuilds the tree from the merged leaf set (an error then leaves the old tree as it was).  On a context with a 64-byte digest the
+ * hash chain is laid again afterwards.  Unlike three calls to dapol_tree_remove / _insert / _update, a refusal of any part leaves no
+ * part applied. */
+int32_t dapol_tree_apply(dapol_tree* tree, size_t n_remove, const uint64_t* remove_idx, size_t n_put, const uint64_t* put_idx,
+                         const uint64_t* put_v, const uint8_t* put_r32, uint8_t* put_was_new);
+/* What the last dapol_tree_update / dapol_tree_insert / dapol_tree_remove / dapol_tree_apply on this tree did: 0 = rebuilt, 1 = replaced
+ * existing leaves in place, 2 = inserted new leaves in place (disjoint chains), 3 = both, 4 = removed leaves in place, 5 = inserted new
+ * leaves in place by dapol_tree_insert's general path, 6 = applied in place by dapol_tree_apply (diagnostics; the tree is the same
+ * whichever path ran). */
 int32_t dapol_tree_last_update_path(dapol_tree* tree, int32_t* path);
 /* Dapol::root_raw / Dapol::root (src/dapol/mod.rs:134-141). Any out pointer may be NULL. */
 int32_t dapol_tree_root(dapol_tree* tree, uint8_t C32[32], uint8_t H32[32], uint64_t* v, uint8_t r32[32]);
