@@ -300,7 +300,8 @@ static int32_t queue_chunk(dapol_ctx* ctx, const ProvePlan& P, const ProveLane& 
         hipLaunchKernelGGL(k_rp_final, dim3(g_lane), dim3(64), 0, st, A, d_err); LAUNCH_CHECK();
         return DAPOL_OK;
     }
-    if (P.gs_mat) hipLaunchKernelGGL(k_rp_mat_prep_gs, dim3(g_gsdig), dim3(64), 0, st, A);
+    if (P.prep_share) hipLaunchKernelGGL(k_rp_mat_prep_gs_shared, dim3(nblk(cb * (size_t)(2 * (A.N / A.tail_n)), 64)), dim3(64), 0, st, A);
+    else if (P.gs_mat) hipLaunchKernelGGL(k_rp_mat_prep_gs, dim3(g_gsdig), dim3(64), 0, st, A);
     else hipLaunchKernelGGL(k_rp_mat_prep, dim3(g_dig), dim3(64), 0, st, A);
     LAUNCH_CHECK();
     if (tm) HIPCHK(tm->mark(st, 1));
@@ -370,6 +371,7 @@ static int32_t range_prove_device(dapol_ctx* ctx, int n, int m, size_t B, const 
     A.out_words = 72 + 16 * A.lgN;
     A.seed = d_seed; A.slot_base = slot_base;
     A.wbits = s.wbits; A.nwin = s.nwin;
+    A.prep = (P.prep_recode ? PREP_RECODE : 0) | (P.prep_share ? PREP_SHARE : 0);
     A.tail_n = P.tail_n; A.use_hi = P.use_hi ? 1 : 0; A.fs_parts = P.fs_parts; A.mat_round = P.nf_rounds();
     A.stream_id = d_stream;                                  // (row-indexed from the call's first proof: RangeArgs::p0)
     A.tape_stride = (uint32_t)(tape_stride ? tape_stride : slots);

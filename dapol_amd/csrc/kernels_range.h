@@ -28,6 +28,7 @@ struct ProofState {             // per proof, lives in HBM between phase kernels
 struct RangeArgs {
     int n, m, N, lgN, TP;       // bits per party, parties, n*m, log2 N, digit-row length (>= 64)
     int wbits, nwin;            // window width of the context's tables; windows per CANONICAL scalar (tv.nwin_c())
+    int prep;                   // PREP_* bits: which forms of the digit producers this call runs (ProvePlan::prep_recode / prep_share)
     size_t B;                   // proofs in this chunk
     // inputs
     const uint64_t* vals;       // [B][m]
@@ -79,6 +80,10 @@ struct RangeArgs {
 enum { TAIL_WBITS = DAPOL_TAIL_WBITS, TAIL_NWIN = 253 / TAIL_WBITS + 1, TAIL_ENTRIES = (1 << (TAIL_WBITS - 1)) + 1, TAIL_ROW_WORDS = TAIL_ENTRIES * 32 };
 enum { MSM_PLAIN = 0, MSM_MATERIALIZE = 1, MSM_TAIL = 2 };
 enum { STAB_ROUNDS = 6, STAB_N = 1 << STAB_ROUNDS };      // coefficient tables serve arguments that need at most TG_6 (64 entries)
+// RangeArgs::prep.  PREP_RECODE: the sweep's producers recode with the unrolled extraction where the window geometry is a compiled
+// one (write_digits_gs).  PREP_SHARE: the materialisation's scalars are written once per (side, k) instead of once per generator
+// (k_rp_mat_prep_gs_shared), which leaves y^i H'_i in the tail's H rows and y^-i in the tail's s2 (tail_row_vectors).
+enum { PREP_RECODE = 1, PREP_SHARE = 2 };
 
 __device__ __forceinline__ void proof_row(const RangeArgs& A, size_t b, size_t& e, uint32_t& j) {
     const size_t g = A.p0 + b;
@@ -181,7 +186,7 @@ __device__ __forceinline__ void coeff_times(sc& p, const RangeArgs& A, size_t b,
         ld_sc(t, T);
         if (isH) {
             sc yi, q;
-            ld_sc(yi, A.s2 + b * A.N + j);            // y^-j, plain (k_rp_lr); ones in the tail argument
+            ld_sc(yi, A.s2 + b * A.N + j);            // y^-j, plain (k_rp_lr); in the tail argument ones, or y^-j again (PREP_SHARE)
             sc_montmul(q, v, yi);                      // Montgomery x plain = plain v y^-j
             sc_montmul(p, q, t);                       // plain x Montgomery = plain
         } else sc_montmul(p, v, t);                    // Montgomery x plain
@@ -589,13 +594,16 @@ __device__ __forceinline__ void build_niels_row(int32_t* row) {
 }
 
 // The tail argument's vectors of row g (G'_g for g < T, else H'_(g-T)) of proof b: a, b = the first T entries of the folded
-// vectors, coefficients s = 1.
+// vectors, coefficients s = 1.  PREP_SHARE: the H rows were materialised as y^i H'_i (the factor y^-i left out of the shared
+// scalars, k_rp_mat_prep_gs_shared), so the tail's H coefficients start from y^-i -- the main argument's s2, which table mode
+// never rewrites -- and every product of the tail rounds is the same group element as before.
 __device__ __forceinline__ void tail_row_vectors(const RangeArgs& A, size_t b, int g) {
     const int T = A.tail_n;
     sc one, v;
     sc_zero(one); one.v[0] = 1;                              // plain 1 (the s-vectors are kept in plain form)
     int i = g < T ? g : g - T;
     if (g == 0) stab_init(A, b);                             // the tail argument starts from coefficient 1 on both sides
+    if (g >= T && (A.prep & PREP_SHARE)) ld_sc(one, A.s2 + b * A.N + i);      // y^-i, plain (k_rp_lr)
     st_sc((g < T ? A.tail_s1 : A.tail_s2) + b * T + i, one);
     ld_sc(v, (g < T ? A.a : A.b) + b * A.N + i);
     st_sc((g < T ? A.tail_a : A.tail_b) + b * T + i, v);

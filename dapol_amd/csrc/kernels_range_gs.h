@@ -26,11 +26,18 @@ namespace dapol {
 // Signed radix-2^W digits of ONE canonical scalar (the term at sweep position sp of proof p): component sp & 3 of the quad's
 // 16-byte element, one 4-byte store per window.  Same recoding as sc_recode_w; the scalar is shifted down a window at a time
 // (static register indexes only).
+// PREP_RECODE: the window geometries the library's tables are built with by default -- 17 bits (15 windows) and 16 bits (16) -- take
+// sc_recode_fixed instead, where a window is one or two words at fixed indexes: the eight-word shift per window, most of the loop
+// below, is gone.  Same digits; every other width keeps the loop.
 __device__ __forceinline__ void write_digits_gs(const RangeArgs& A, size_t p, int sp, const uint32_t* c) {
     const size_t L = A.B * (size_t)A.nwin;
     int32_t* out = reinterpret_cast<int32_t*>(A.dig) + ((((size_t)(sp >> 2)) * L + p) << 2) + (sp & 3);
     const size_t wstride = A.B * (size_t)4;
     const int W = A.wbits, NW = A.nwin, half = 1 << (W - 1);
+    if (A.prep & PREP_RECODE) {                            // (uniform over the launch)
+        if (W == 17 && NW == 15) { sc_recode_fixed<17, 15>(c, [&](int w, int digit) { out[(size_t)w * wstride] = digit; }); return; }
+        if (W == 16 && NW == 16) { sc_recode_fixed<16, 16>(c, [&](int w, int digit) { out[(size_t)w * wstride] = digit; }); return; }
+    }
     const uint32_t mask = (1u << W) - 1;
     uint32_t x[8];
 #pragma unroll
@@ -261,7 +268,8 @@ __global__ __launch_bounds__(64) void k_rp_gs_combine(RangeArgs A, const int32_t
 // of their high-half rows when the context has them (TableView::hi_split: window w and window w + hi_split in the same lane) --
 // and a lane owns (proof, window) of that class.  A class's LW window sums are combined by k_rp_mat_gs_horner, MAT_GROUP classes
 // per launch so that the Horner chains (W (LW - 1) doublings, the same work the proof-stationary kernel does) fill the chip.
-// Digits: sweep position sp = side * N + i * (N / T) + k  <->  term q = i + k T, same dig4 layout as above.
+// Digits: sweep position sp = side * N + i * (N / T) + k  <->  term q = i + k T, same dig4 layout as above; with PREP_SHARE the
+// scalars of (side, k) at sp = side * (N / T) + k serve every class i (k_rp_mat_prep_gs_shared).
 enum { MAT_GROUP = 16 };
 // accumulator slots of a chunk (MAT_GROUP classes, or 2 lists x up to GS_MAX_SLICES slices); lanes that fill the chip (3,072 wavefronts)
 enum { GS_ACC_SLOTS = 32, GS_MAX_SLICES = 16, GS_FULL_LANES = 3072 * 64 };
@@ -279,6 +287,22 @@ __global__ __launch_bounds__(64) void k_rp_mat_prep_gs(RangeArgs A) {
         coeff_plain(s, A, p, A.mat_round, cls + k * A.tail_n, side != 0);          // plain form
         write_digits_gs(A, p, sp, s.v);
     }
+}
+// PREP_SHARE (table mode only): after mat_round rounds the coefficient of generator q = cls + k T is TG[k] on the G side and
+// y^-cls * (y^-kT TH[k]) on the H side, so with y^-cls left to the tail (tail_row_vectors) every class of a side has the SAME N / T
+// scalars.  They are written once, at sweep positions side * (N / T) + k of the same dig4 layout -- the head of the digit matrix --
+// and k_rp_mat_gs reads every class's digits from there: 2 N / T scalars a proof instead of 2 N.
+// grid = ceil(cb * 2 (N / T) / 64) blocks of 64; quads of positions on adjacent lanes, then the proofs, as gs_thread.
+__global__ __launch_bounds__(64) void k_rp_mat_prep_gs_shared(RangeArgs A) {
+    const int per = A.N / A.tail_n;
+    const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const size_t quad = t >> 2, sp4 = quad / A.B, p = quad - sp4 * A.B;
+    if (sp4 >= (size_t)(2 * per) / 4) return;
+    const int sp = (int)(4 * sp4) + (int)(t & 3);
+    const int side = sp >= per ? 1 : 0, k = sp - side * per;
+    sc s;
+    coeff_plain(s, A, p, A.mat_round, k * A.tail_n, side != 0);                    // TG[k], or y^-kT TH[k]; plain form
+    write_digits_gs(A, p, sp, s.v);
 }
 
 // One class, one half (0: the generators' own rows, digits of window w; 1: their high-half rows, digits of window w + LW).
@@ -305,7 +329,8 @@ __global__ __launch_bounds__(64, DAPOL_GS_OCC) void k_rp_mat_gs(RangeArgs A, Tab
         }
     }
     const int per = A.N / A.tail_n;
-    const dapol_v4i* dg = reinterpret_cast<const dapol_v4i*>(A.dig) + ((size_t)(side * A.N + cls * per) >> 2) * L + (size_t)wd * A.B + p;
+    // (PREP_SHARE: the scalars of (side, k) serve every class -- k_rp_mat_prep_gs_shared)
+    const dapol_v4i* dg = reinterpret_cast<const dapol_v4i*>(A.dig) + ((size_t)((A.prep & PREP_SHARE) ? side * per : side * A.N + cls * per) >> 2) * L + (size_t)wd * A.B + p;
     dapol_v4i d4 = dg[0], dn = d4;                       // (digits one quad ahead, as in k_rp_msm_gs)
 #pragma nounroll
     for (int k = 0; k < per; k++) {

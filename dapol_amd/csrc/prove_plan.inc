@@ -12,6 +12,9 @@
 enum { FS_PARTS_MAX = 8 };        // most wavefronts per proof of k_rp_poly / k_rp_lr in small calls
 enum { TAIL_RPL_DEFAULT = 4 };    // the plan's own choice of ProvePlan::tail_rpl for full chunks (1 or 4)
 enum { TAIL_GS_DEFAULT = 1 };     // the plan's own choice of ProvePlan::tail_gs for full chunks (0: only DAPOL_TAIL_ORDER=gs turns it on)
+#ifndef DAPOL_PREP_V2_PARTS
+#define DAPOL_PREP_V2_PARTS 3     // what DAPOL_PREP=v2 turns on: 1 = ProvePlan::prep_recode, 2 = prep_share (a build of one part alone: how each was measured)
+#endif
 
 struct ProveShape {
     int n, m;
@@ -51,6 +54,10 @@ struct ProvePlan {
     // Rows of the proof's tail table a lane of k_rp_tail_table builds: 1, or 4 with one field inversion between them
     // (k_rp_tail_table4); set by finalise().  tail_rpl_forced: DAPOL_TAIL_ROWS_PER_LANE = 1 / 4 (0: the plan's choice).
     int tail_rpl, tail_rpl_forced;
+    // DAPOL_PREP = v1 / v2 (default v2): the digit producers of a swept call as they were, or prep_recode: the unrolled recode of the
+    // compiled window geometries (write_digits_gs); prep_share: the materialisation's scalars once per (side, k)
+    // (k_rp_mat_prep_gs_shared) -- swept materialisation in table mode only.  Neither moves a byte of the scratch layout.
+    bool prep_recode, prep_share;
     // what the per-chunk choices below start from
     int gs_tile, gs_slices_forced, mat_cpl_forced;
     bool gs_tile_set, a_lane_ok;
@@ -322,6 +329,12 @@ static ProvePlan plan_range_prove(const ProveShape& s) {
     if (!gs_possible) gs = false;                            // (no accumulators were counted into the scratch)
     P.gs = gs;
     P.gs_mat = gs && tail_n && (N / tail_n) % 4 == 0 && !knob("DAPOL_NO_GS_MAT");
+    {
+        const char* const e = knob("DAPOL_PREP");
+        const int parts = (e && e[0] == 'v' && e[1] == '1' && !e[2]) ? 0 : DAPOL_PREP_V2_PARTS;     // (anything but v1 is no value)
+        P.prep_recode = gs && (parts & 1);
+        P.prep_share = P.gs_mat && P.stab_main && (parts & 2);
+    }
     P.gs_tile = s.gs_tile_rows > 0 ? s.gs_tile_rows : 16;
     const char* const e_tile = knob("DAPOL_GS_TILE");
     P.gs_tile_set = s.gs_tile_rows > 0 || e_tile;

@@ -344,5 +344,22 @@ DAPOL_HD void sc_recode_w(int W, int NW, const uint32_t* x, F out) {
         out(i, b - (carry << W));
     }
 }
+// The same digits with W and NW known at compile time: fully unrolled, every window is an extract at fixed word indexes and fixed
+// shifts (a scalar held in registers is neither indexed by a run-time value nor shifted down a window at a time); the second word is
+// fetched only for the windows that cross a word boundary.  Same carry rule.
+template <int W, int NW, typename F>
+DAPOL_HD void sc_recode_fixed(const uint32_t* x, F out) {
+    static_assert(W >= 2 && W <= 31 && NW >= 1 && W * (NW - 1) < 256, "window geometry");
+    int carry = 0;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const int o = i * W, wd = o >> 5, sh = o & 31;
+        uint32_t v = x[wd] >> sh;
+        if (sh + W > 32 && wd + 1 < 8) v |= x[wd + 1] << (32 - sh);
+        const int b = (int)(v & ((1u << W) - 1)) + carry;
+        carry = (i < NW - 1 && b >= (1 << (W - 1))) ? 1 : 0;
+        out(i, b - (carry << W));
+    }
+}
 
 }  // namespace dapol
