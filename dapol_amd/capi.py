@@ -130,6 +130,14 @@ _SIG = {
                                                              _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P]),
     "dapol_verify_entities_compact": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, ctypes.c_int32,
                                                        ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P]),
+    "dapol_compact_paths_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, _P]),
+    "dapol_compact_paths_expand": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, ctypes.c_size_t,
+                                                    ctypes.c_size_t, _P, _P]),
+    "dapol_compact_paths_compress": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dapol_tree_paths_compact": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dapol_verify_entities_compact_paths": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, ctypes.c_int32,
+                                                             ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P, _P]),
+    "dapol_diag_compact_paths": (ctypes.c_int32, [_P, _P]),
     "dapol_reprove_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
     "dapol_reprove_entities_shared": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P,
                                                        _P, _P]),
@@ -484,6 +492,26 @@ class Context:
                                                  policy, aggregation_factor, n_bits, _ptr(cp), cp.shape[0], _ptr(seed), _ptr(ok), ctypes.byref(unique)))
         return ok, int(unique.value)
 
+    def verify_entities_compact_paths(self, height, leaf_idx, leaf_C, leaf_H, cpath_C, cpath_H, root_C, root_H, policy, aggregation_factor, n_bits, compact,
+                                      verify_seed=None):
+        """dapol_verify_entities_compact_paths: verify_entities_compact's verdicts over compact_paths_expand(cpath), every distinct node
+        of the paths merged once.  Returns (ok, unique, path_merges): unique = range proofs actually checked, path_merges = merges made
+        (the record count when sharing answered the call)."""
+        leaf_idx = _u64(leaf_idx)
+        b = leaf_idx.shape[0]
+        lC, lH = _u8(leaf_C, b, 32), _u8(leaf_H, b, self.hb)
+        cC, cH = _u8(cpath_C).reshape(-1, 32), _u8(cpath_H).reshape(-1, self.hb)
+        cp = _u8(compact).reshape(-1)
+        rC, rH = _u8(np.frombuffer(root_C, np.uint8)), _u8(np.frombuffer(root_H, np.uint8))
+        seed = _u8(np.frombuffer(verify_seed, np.uint8)) if verify_seed is not None else None   # None: the library draws one from the OS
+        ok, unique, merges = np.zeros(b, np.uint8), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if cH.shape[0] != cC.shape[0]:
+            return ok, 0, 0
+        _chk(lib().dapol_verify_entities_compact_paths(self.h, height, b, _ptr(leaf_idx), _ptr(lC), _ptr(lH), cC.shape[0], _ptr(cC), _ptr(cH), _ptr(rC), _ptr(rH),
+                                                       policy, aggregation_factor, n_bits, _ptr(cp), cp.shape[0], _ptr(seed), _ptr(ok), ctypes.byref(unique),
+                                                       ctypes.byref(merges)))
+        return ok, int(unique.value), int(merges.value)
+
     def verify_batch(self, height, leaf_idx, leaf_C, leaf_H, sib_C, sib_H, root_C, root_H, policy, aggregation_factor, n_bits, range_proofs,
                      verify_seed=None):
         """DapolProof::verify_batch: one proof covering k leaves."""
@@ -540,6 +568,52 @@ def shared_plan(height, leaf_idx, policy, aggregation_factor):
     _chk(lib().dapol_shared_plan(height, leaf_idx.shape[0], _ptr(leaf_idx), policy, aggregation_factor, _ptr(n_sub), ctypes.byref(tot), ctypes.byref(per)))
     b = leaf_idx.shape[0]
     return n_sub[:per.value // b if b else 0], int(tot.value), int(per.value)
+
+
+def compact_paths_plan(height, leaf_idx, want_ref=True):
+    """dapol_compact_paths_plan (host-only): (depth_off [height + 2] record offsets per depth, ref [height][b] = the record of its depth
+    that each row uses (None without want_ref), the record count)."""
+    leaf_idx = _u64(leaf_idx)
+    b = leaf_idx.shape[0]
+    depth_off = np.zeros(max(height, 0) + 2, np.uint64)
+    ref = np.zeros((max(height, 0), b), np.uint32) if want_ref else None
+    n = ctypes.c_uint64(0)
+    _chk(lib().dapol_compact_paths_plan(height, b, _ptr(leaf_idx), _ptr(depth_off), _ptr(ref), ctypes.byref(n)))
+    return depth_off, ref, int(n.value)
+
+
+def compact_paths_expand(height, leaf_idx, cpath_C, cpath_H, first=0, count=None, hash_bytes=32):
+    """dapol_compact_paths_expand (host-only): rows [first, first + count) (count None: to the end) of the compact path buffer as
+    (path_C [count][height][32], path_H [count][height][hash_bytes]) under the process's sibling order."""
+    leaf_idx = _u64(leaf_idx)
+    b = leaf_idx.shape[0]
+    count = b - first if count is None else count
+    cC, cH = _u8(cpath_C).reshape(-1, 32), _u8(cpath_H).reshape(-1, hash_bytes)
+    if cC.shape[0] != cH.shape[0]:
+        raise DapolError(8, "cpath_C and cpath_H hold different numbers of records")
+    pC, pH = np.zeros((max(count, 0), max(height, 0), 32), np.uint8), np.zeros((max(count, 0), max(height, 0), hash_bytes), np.uint8)
+    _chk(lib().dapol_compact_paths_expand(hash_bytes, height, b, _ptr(leaf_idx), _ptr(cC), _ptr(cH), cC.shape[0], first, count, _ptr(pC), _ptr(pH)))
+    return pC, pH
+
+
+def compact_paths_compress(height, leaf_idx, path_C, path_H, hash_bytes=32):
+    """dapol_compact_paths_compress (host-only): the compact path buffer (cpath_C [n][32], cpath_H [n][hash_bytes]) of expanded paths
+    [b][height] (the first row of every run)."""
+    leaf_idx = _u64(leaf_idx)
+    b = leaf_idx.shape[0]
+    n = ctypes.c_uint64(0)
+    _chk(lib().dapol_compact_paths_plan(height, b, _ptr(leaf_idx), None, None, ctypes.byref(n)))
+    pC, pH = _u8(path_C, b, height, 32), _u8(path_H, b, height, hash_bytes)
+    cC, cH = np.zeros((n.value, 32), np.uint8), np.zeros((n.value, hash_bytes), np.uint8)
+    _chk(lib().dapol_compact_paths_compress(hash_bytes, height, b, _ptr(leaf_idx), _ptr(pC), _ptr(pH), _ptr(cC), _ptr(cH), n.value, ctypes.byref(n)))
+    return cC, cH
+
+
+def diag_compact_paths():
+    """dapol_diag_compact_paths: (device ms of the path stage of the last verify_entities_compact_paths, its route)."""
+    ms, route = ctypes.c_double(0.0), ctypes.c_int32(0)
+    _chk(lib().dapol_diag_compact_paths(ctypes.byref(ms), ctypes.byref(route)))
+    return ms.value, route.value
 
 
 def shared_compact_plan(height, leaf_idx, policy, aggregation_factor, n_bits):
@@ -836,6 +910,18 @@ class Tree:
         v = np.zeros((b, h), np.uint64)
         _chk(lib().dapol_tree_paths(self.h, b, _ptr(leaf_idx), _ptr(C), _ptr(H), _ptr(v), _ptr(r)))
         return C, H, v, r
+
+    def paths_compact(self, leaf_idx):
+        """dapol_tree_paths_compact: the compact path buffer (cpath_C [n][32], cpath_H [n][digest bytes]) of the paths of strictly
+        increasing leaves: every distinct sibling once (compact_paths_expand gives paths()' C and H)."""
+        leaf_idx = _u64(leaf_idx)
+        b = leaf_idx.shape[0]
+        n = ctypes.c_uint64(0)
+        if lib().dapol_compact_paths_plan(self.height, b, _ptr(leaf_idx), None, None, ctypes.byref(n)) != 0:
+            n = ctypes.c_uint64(0)                            # (the call below reports what is wrong with the indexes)
+        cC, cH = np.zeros((n.value, 32), np.uint8), np.zeros((n.value, self.ctx.hb), np.uint8)
+        _chk(lib().dapol_tree_paths_compact(self.h, b, _ptr(leaf_idx), _ptr(cC), _ptr(cH), n.value, ctypes.byref(n)))
+        return cC[:n.value], cH[:n.value]
 
     def prove_batch(self, leaf_idx, policy, aggregation_factor, n_bits, nonce_seed):
         """Dapol::generate_proof_batch: one proof for all the leaves.  Returns (sib_level, sib_index, sib_C, sib_H, range blob)."""

@@ -23,6 +23,7 @@
 #include "kernels_verify_compact.h"
 #include "kernels_reprove.h"
 #include "kernels_store.h"
+#include "kernels_compact_paths.h"
 
 using namespace dapol;
 
@@ -482,6 +483,7 @@ int32_t dapol_commit_hash_batch(dapol_ctx* ctx, size_t n, const uint64_t* v, con
 #include "host_verify.inc"
 #include "host_verify_shared.inc"
 #include "host_verify_compact.inc"
+#include "host_compact_paths.inc"
 #include "host_store.inc"
 #include "host_leaf.inc"
 #include "host_wire.inc"

@@ -694,6 +694,72 @@ class Dapol {
         for (size_t e = 0; e < b; e++) out[e] = ok[e] != 0;
         return {out, unique};
     }
+    // COMPACT Merkle paths (dapol_tree_paths_compact): every distinct sibling of the paths of `leaves` once, root side first, in the
+    // layout of dapol_compact_paths_plan -- what verify_proofs_compact_paths takes.  expand() cuts the paths of single leaves out.
+    struct CompactPaths {
+        std::vector<uint64_t> leaves;                    // strictly increasing
+        std::vector<uint8_t> com, hash;                  // [records][32] each
+        int height = 0;
+        size_t records() const { return com.size() / 32; }
+        // the siblings of rows [first, first + count) as generate_proof returns them (count = 1: one user's path)
+        std::vector<std::vector<DapolProofNode>> expand(size_t first, size_t count) const {
+            const size_t h = (size_t)height;
+            std::vector<uint8_t> C(count * h * 32 + 1), H(count * h * 32 + 1);
+            std::vector<uint8_t> cC(com), cH(hash);
+            cC.push_back(0); cH.push_back(0);                                 // never pass a null data pointer
+            check(dapol_compact_paths_expand(32, height, leaves.size(), leaves.data(), cC.data(), cH.data(), records(), first, count, C.data(), H.data()));
+            std::vector<std::vector<DapolProofNode>> out(count, std::vector<DapolProofNode>(h));
+            for (size_t e = 0; e < count; e++)
+                for (size_t s = 0; s < h; s++) {
+                    std::memcpy(out[e][s].com.data(), &C[(e * h + s) * 32], 32);
+                    std::memcpy(out[e][s].hash.data(), &H[(e * h + s) * 32], 32);
+                }
+            return out;
+        }
+        std::vector<std::vector<DapolProofNode>> expand() const { return expand(0, leaves.size()); }
+    };
+    // nullopt: no liability at one of the leaves.  Plain trees (no upper siblings).
+    std::optional<CompactPaths> generate_paths_compact(const std::vector<uint64_t>& leaves) const {
+        const size_t b = leaves.size();
+        uint64_t n = 0;
+        if (dapol_compact_paths_plan(height_, b, leaves.data(), nullptr, nullptr, &n) != DAPOL_OK) n = 0;      // (the call below says what is wrong with the leaves)
+        int32_t rc;
+        CompactPaths out;
+        out.com.resize((size_t)n * 32 + 1); out.hash.resize((size_t)n * 32 + 1);
+        rc = dapol_tree_paths_compact(tree_.get(), b, leaves.data(), out.com.data(), out.hash.data(), (size_t)n, &n);
+        if (rc == DAPOL_ERR_UNKNOWN_LEAF) return std::nullopt;
+        check(rc);
+        out.com.resize((size_t)n * 32); out.hash.resize((size_t)n * 32);
+        out.leaves = leaves;
+        out.height = height_;
+        return out;
+    }
+    // dapol_verify_entities_compact_paths: verify_proofs_compact's verdicts with paths.expand() as the Merkle siblings (those of `proofs`
+    // are not read), every distinct node of the paths merged once.  Returns the verdicts, the range proofs actually checked and the
+    // merges made (paths.records() when sharing answered the call).
+    struct CompactPathsVerdict { std::vector<bool> ok; uint64_t unique = 0, path_merges = 0; };
+    static CompactPathsVerdict verify_proofs_compact_paths(const Context& ctx, const DapolProofNode& root, const std::vector<DapolProofNode>& leaves,
+                                                           const CompactProofs& proofs, const CompactPaths& paths, const uint8_t* verify_seed32 = nullptr) {
+        const size_t b = proofs.leaves.size();
+        if (leaves.size() != b || paths.leaves != proofs.leaves || paths.height != proofs.height || paths.hash.size() != paths.com.size())
+            throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        CompactPathsVerdict out;
+        out.ok.assign(b, false);
+        if (b == 0) return out;
+        std::vector<uint8_t> lC(b * 32), lH(b * 32), C(paths.com), H(paths.hash), R(proofs.compact);
+        for (size_t e = 0; e < b; e++) {
+            std::memcpy(&lC[e * 32], leaves[e].com.data(), 32);
+            std::memcpy(&lH[e * 32], leaves[e].hash.data(), 32);
+        }
+        const size_t r_len = R.size();
+        C.push_back(0); H.push_back(0); R.push_back(0);                     // never pass a null data pointer
+        std::vector<uint8_t> ok(b, 0);
+        check(dapol_verify_entities_compact_paths(ctx.get(), proofs.height, b, proofs.leaves.data(), lC.data(), lH.data(), paths.records(), C.data(), H.data(),
+                                                  root.com.data(), root.hash.data(), (int)proofs.policy, (int)proofs.aggregation_factor, proofs.n_bits, R.data(),
+                                                  r_len, verify_seed32, ok.data(), &out.unique, &out.path_merges));
+        for (size_t e = 0; e < b; e++) out.ok[e] = ok[e] != 0;
+        return out;
+    }
   private:
     static std::pair<std::vector<bool>, uint64_t> verify_many_shared(const Context& ctx, const DapolProofNode& root, const std::vector<DapolProofNode>& leaves,
                                                                      const std::vector<DapolProof>& proofs, const uint8_t* verify_seed) {

@@ -685,6 +685,69 @@ int32_t dapol_verify_entities_compact(dapol_ctx* ctx, int32_t height, size_t b, 
                                       const uint8_t root_H32[32], int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint8_t* compact,
                                       size_t compact_len, const uint8_t verify_seed32[32], uint8_t* ok, uint64_t* unique_subproofs_out);
 
+/* COMPACT Merkle paths: every distinct sibling of a call's paths leaves the prover and enters the verifier ONCE.
+ *   The form.  For strictly increasing leaf_idx [b] below 2^height, H = height in 1 .. 64: key_d(e) = leaf_idx[e] >> (H - d) for
+ * d = 1 .. H and key_0 = 0.  The sibling of row e at depth d is the node (d, key_d(e) ^ 1): rows that share key_d share it.  Row e is a
+ * HEAD at depth d iff e = 0 or key_d(e) != key_d(e - 1); a head at d is a head at every deeper depth.  The COMPACT PATH BUFFER is laid
+ * out for d = 1 .. H, root side first, ALWAYS (it does not depend on dapol_wire_config.siblings_leaf_first): for each depth the
+ * n_unique[d] records (C [32], H [hash_bytes]) of the siblings of the distinct keys of depth d, in ascending key order, as two arrays
+ * cpath_C32 [n_records][32] and cpath_H [n_records][hash_bytes].  depth_off[d] = the record offset of depth d (depth_off[0] =
+ * depth_off[1] = 0, depth_off[H + 1] = n_records), ref[d][e] = (distinct keys of depth d among rows 0 .. e) - 1.  Expansion gives
+ * dapol_tree_paths' [b][H] arrays, and it is the expansion that honours siblings_leaf_first.  A sibling that is also an ancestor of
+ * another row is still a record: this is deduplication, not a multiproof, and the per-entity meaning of a path does not change.
+ *   Host-only (no GPU, no context):
+ *   dapol_compact_paths_plan: depth_off [height + 2], ref [height][b] (ref[(d - 1) * b + e]), *n_records; every out pointer may be NULL.
+ *   dapol_compact_paths_expand: rows [first, first + count) as path_C32_out [count][height][32], path_H_out [count][height][hash_bytes];
+ * count = 1 cuts one user's path out.
+ *   dapol_compact_paths_compress: the inverse; it writes the first row of every run and does not read the other rows.
+ *   Refusals: indexes that are not strictly increasing or not below 2^height, hash_bytes other than 32 or 64, an n_records that is not
+ * the layout's, first + count > b, a cap_records below the layout's -> DAPOL_ERR_INVALID_ARGUMENT with nothing written.  b = 0 is
+ * DAPOL_OK with n_records = 0.
+ *   dapol_tree_paths_compact: the compact buffer of the paths of b leaves, written from the tree's levels on the device: every row
+ * walks its chain as dapol_tree_paths does and stores a record only at the depths at which it is a head.  No [b][H] array exists on
+ * the device and only the records cross the bus.  cpath_H32 holds dapol_ctx_digest_bytes per record.  The length is checked on the
+ * host before anything is queued (cap_records below it -> DAPOL_ERR_INVALID_ARGUMENT); an unknown leaf -> DAPOL_ERR_UNKNOWN_LEAF;
+ * nothing is written in either case.  dapol_compact_paths_expand of the output equals dapol_tree_paths' (C, H) byte for byte.  The
+ * provers accept path_C32 = path_H32 = NULL: a caller that wants compact paths passes NULL there and calls this.  Plain trees only (no
+ * n_upper: a shard's upper siblings are one record each, which the caller can prepend).
+ *   dapol_verify_entities_compact_paths: dapol_verify_entities_compact over compact paths.
+ *   Definition.  ok[] equals what dapol_verify_entities_compact returns for the same leaves, root and compact proofs with
+ * dapol_compact_paths_expand(cpath) as the paths -- for every input, tampered ones included.  A wrong n_records or compact_len gives
+ * ok = 0, both counters 0 and DAPOL_OK; indexes that are not strictly increasing and below 2^height give DAPOL_ERR_INVALID_ARGUMENT,
+ * as does a context with a 64-byte node digest.  Calls with b x plan size <= 64 expand on the host, forward to
+ * dapol_verify_entities_compact and report *path_merges_out = b x height.
+ *   Every distinct node (d, key) of the call's paths is merged with its record once: canonically where the head row of (d, key) is
+ * also the head row of its parent (the result, extended point included, becomes the parent's value: a point this call has made is
+ * never decoded again), as a JOIN where it is not (the result is compared, C and H, with the parent's canonical value).  If every
+ * decoding succeeds, every join matches and row 0's chain ends in the root, every per-entity chain is the same function of the same
+ * inputs as a chain that was checked, and every path verifies: *path_merges_out = n_records.  Otherwise the paths are expanded on the
+ * device and the per-entity re-merge of dapol_verify_entities runs over them as it is (a non-canonical record fails exactly the rows
+ * whose own path holds it; a join that fails says nothing about which of its two rows is wrong): *path_merges_out = n_records +
+ * b x height.  The range proofs take the compact verifier's groups; a statement's commitments are read from the records that its
+ * head row walks, so equal subtree keys imply equal commitments and *unique_subproofs_out = dapol_shared_plan's total on any input.
+ *   dapol_diag_compact_paths: device time of the path stage of the last such call on any context (events around its path launches)
+ * and its route (0 forwarded, 1 shared merges, 2 shared merges then the fallback, 3 the fallback alone -- a test knob).
+ *   When to use it (tools/bench_compact_paths.py, DESIGN.md section 4.6, profiles/compact_paths_2e18_h30.json: 2^18 leaves at height
+ * 30, 64-bit proofs, one MI355X, whole calls against dapol_verify_entities_compact fed the expanded paths): random leaves, x2.29 fewer
+ * records: padding / 30 0.102 -> 0.085 s (x1.19), padding / 16 0.378 -> 0.326 s (x1.16), padding / 0 0.383 -> 0.329 s (x1.17);
+ * consecutive leaves, x15 fewer records: 0.101 -> 0.074 s, 0.089 -> 0.057 s, 0.091 -> 0.059 s.  The path stage itself: 16.8 ms per
+ * entity -> 10.4 ms (random) / 5.4 ms (consecutive) shared.  dapol_tree_paths_compact against dapol_tree_paths: 10.9 -> 10.0 ms and
+ * 503 -> 220 MB returned (random), 10.8 -> 3.0 ms and 503 -> 34 MB (consecutive).  It gains at every aggregation factor, padding /
+ * height included; a call in which anything fails to verify pays the shared merges and then the per-entity ones. */
+int32_t dapol_compact_paths_plan(int32_t height, size_t b, const uint64_t* leaf_idx, uint64_t* depth_off, uint32_t* ref, uint64_t* n_records);
+int32_t dapol_compact_paths_expand(int32_t hash_bytes, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* cpath_C32, const uint8_t* cpath_H,
+                                   size_t n_records, size_t first, size_t count, uint8_t* path_C32_out, uint8_t* path_H_out);
+int32_t dapol_compact_paths_compress(int32_t hash_bytes, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* path_C32, const uint8_t* path_H,
+                                     uint8_t* cpath_C32_out, uint8_t* cpath_H_out, size_t cap_records, uint64_t* n_records_out);
+int32_t dapol_tree_paths_compact(dapol_tree* tree, size_t b, const uint64_t* leaf_idx, uint8_t* cpath_C32, uint8_t* cpath_H32, size_t cap_records,
+                                 uint64_t* n_records_out);
+int32_t dapol_verify_entities_compact_paths(dapol_ctx* ctx, int32_t height, size_t b, const uint64_t* leaf_idx, const uint8_t* leaf_C32,
+                                            const uint8_t* leaf_H32, size_t n_records, const uint8_t* cpath_C32, const uint8_t* cpath_H32,
+                                            const uint8_t root_C32[32], const uint8_t root_H32[32], int32_t policy, int32_t aggregation_factor,
+                                            int32_t n_bits, const uint8_t* compact, size_t compact_len, const uint8_t verify_seed32[32], uint8_t* ok,
+                                            uint64_t* unique_subproofs_out, uint64_t* path_merges_out);
+int32_t dapol_diag_compact_paths(double* path_ms, int32_t* route);
+
 /* Multi-GPU: one process per GPU, rank g owning the top-level subtree with index prefix g (dapol_tree_build_shard /
  * dapol_workload_create_shard).  The reference has no communication (single process, single thread); the sharded path has
  * exactly one exchange step and one final reduce, both RCCL calls inside this library (librccl.so, over xGMI):
