@@ -116,6 +116,10 @@ _SIG = {
     "dapol_prove_batch": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
     "dapol_verify_batch": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),
+    "dapol_batches_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
+    "dapol_prove_batches": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
+    "dapol_verify_batches": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, _P, _P, _P, _P]),
     "dapol_entity_proof_size": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "dapol_prove_entities_upper": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
                                                     _P, _P, _P, _P, _P, _P, _P]),
@@ -529,6 +533,24 @@ class Context:
                                               policy, aggregation_factor, n_bits, _ptr(rp), rp.shape[0], _ptr(seed), _ptr(ok)))
         return bool(ok[0])
 
+    def verify_batches(self, height, batches, leaf_C, leaf_H, sib_off, sib_C, sib_H, root_C, root_H, policy, aggregation_factor, n_bits, range_off,
+                       range_proofs, verify_seed=None):
+        """dapol_verify_batches: DapolProof::verify_batch for every list of leaves in `batches`, one call; ok[j] is verify_batch's
+        verdict for batch j.  sib_off / range_off are the lengths the caller holds (prove_batches' on honest input)."""
+        nb, off, flat = _pack_batches(batches)
+        K = flat.shape[0]
+        lC, lH = _u8(leaf_C, K, 32), _u8(leaf_H, K, self.hb)
+        so, ro = _u64(sib_off), _u64(range_off)
+        sC, sH, rp = _u8(sib_C).reshape(-1, 32), _u8(sib_H).reshape(-1, self.hb), _u8(range_proofs).reshape(-1)
+        if so.shape[0] != nb + 1 or ro.shape[0] != nb + 1 or sC.shape[0] < int(so[-1]) or sH.shape[0] < int(so[-1]) or rp.shape[0] < int(ro[-1]):
+            raise DapolError(8, "sib_off / range_off must have nb + 1 entries that stay inside the arrays they index")
+        rC, rH = _u8(np.frombuffer(root_C, np.uint8)), _u8(np.frombuffer(root_H, np.uint8))
+        seed = _u8(np.frombuffer(verify_seed, np.uint8)) if verify_seed is not None else None   # None: the library draws one from the OS
+        ok = np.zeros(nb, np.uint8)
+        _chk(lib().dapol_verify_batches(self.h, height, nb, _ptr(off), _ptr(flat), _ptr(lC), _ptr(lH), _ptr(so), _ptr(sC), _ptr(sH), _ptr(rC), _ptr(rH),
+                                        policy, aggregation_factor, n_bits, _ptr(ro), _ptr(rp), _ptr(seed), _ptr(ok)))
+        return ok
+
     def range_verify_batch(self, n_bits, m, proofs, V32, verify_seed=None):
         proofs = _u8(proofs)
         b = proofs.shape[0]
@@ -557,6 +579,26 @@ def batch_siblings(height, leaf_idx):
     level, index = np.zeros(n.value, np.uint8), np.zeros(n.value, np.uint64)
     _chk(lib().dapol_batch_siblings(height, leaf_idx.shape[0], _ptr(leaf_idx), ctypes.byref(n), _ptr(level), _ptr(index)))
     return level, index
+
+
+def _pack_batches(batches):
+    """[[leaf, ...], ...] -> (nb, batch_off [nb + 1], leaf_idx [sum of k]) as the *_batches calls take them."""
+    off = np.zeros(len(batches) + 1, np.uint64)
+    if len(batches):
+        off[1:] = np.cumsum([len(b) for b in batches])
+    flat = np.zeros(int(off[-1]), np.uint64)
+    for j, b in enumerate(batches):
+        flat[int(off[j]):int(off[j + 1])] = _u64(b)
+    return len(batches), off, flat
+
+
+def batches_plan(height, batches, policy, aggregation_factor, n_bits):
+    """dapol_batches_plan (host-only): (n_siblings [nb], sib_off [nb + 1] in sibling records, range_off [nb + 1] in bytes, number of
+    distinct sibling counts = policy calls that prove_batches makes)."""
+    nb, off, flat = _pack_batches(batches)
+    ns, so, ro, ng = np.zeros(nb, np.uint64), np.zeros(nb + 1, np.uint64), np.zeros(nb + 1, np.uint64), ctypes.c_uint64(0)
+    _chk(lib().dapol_batches_plan(height, nb, _ptr(off), _ptr(flat), policy, aggregation_factor, n_bits, _ptr(ns), _ptr(so), _ptr(ro), ctypes.byref(ng)))
+    return ns, so, ro, int(ng.value)
 
 
 def shared_plan(height, leaf_idx, policy, aggregation_factor):
@@ -938,6 +980,20 @@ class Tree:
         _chk(lib().dapol_prove_batch(self.ctx.h, self.h, k, _ptr(leaf_idx), policy, aggregation_factor, n_bits, _ptr(seed), _ptr(C), _ptr(H),
                                      _ptr(out)))
         return level, index, C, H, out.tobytes()
+
+    def prove_batches(self, batches, policy, aggregation_factor, n_bits, nonce_seed):
+        """dapol_prove_batches: Dapol::generate_proof_batch for every list of leaves in `batches`, one call.  Returns (sib_off [nb + 1],
+        range_off [nb + 1], sib_C [sib_off[nb]][32], sib_H, range bytes [range_off[nb]], S-groups): batch j's proof is
+        sib_C[sib_off[j]:sib_off[j + 1]], sib_H likewise and range[range_off[j]:range_off[j + 1]] -- prove_batch's outputs."""
+        nb, off, flat = _pack_batches(batches)
+        _, so, ro, _ = batches_plan(self.height, batches, policy, aggregation_factor, n_bits)
+        T, R = int(so[-1]), int(ro[-1])
+        C, H, out = np.zeros((T, 32), np.uint8), np.zeros((T, 32), np.uint8), np.zeros(R, np.uint8)
+        seed = _u8(np.frombuffer(nonce_seed, np.uint8))
+        ng = ctypes.c_uint64(0)
+        _chk(lib().dapol_prove_batches(self.ctx.h, self.h, nb, _ptr(off), _ptr(flat), policy, aggregation_factor, n_bits, _ptr(seed), _ptr(C), _ptr(H),
+                                       _ptr(out), ctypes.byref(ng)))
+        return so, ro, C, H, out, int(ng.value)
 
     def prove_entities(self, leaf_idx, policy, aggregation_factor, n_bits, nonce_seed, upper=None, tape=None):
         """upper = (C[u,32], H[u,32], v[u], r[u,32]) siblings above a shard root, root side first.

@@ -146,6 +146,39 @@ int32_t dapol_prove_batch(dapol_ctx* ctx, dapol_tree* tree, size_t k, const uint
 // MerkleProof::verify_batch with DapolProofNode::merge: arena slots [0, k) leaves, [k, k + S) siblings, then the
 // merged nodes level by level; `ops` = (left slot, right slot, destination slot).
 struct MergeOp { uint32_t left, right, dst; };
+// The merge schedule of one batch: walk the levels bottom-up; sibling slots are consumed in plan order within their level.  The
+// leaves sit at slots leaf_slot + i, the siblings at sib_slot + i, every merged node takes next_slot++; emit(level, left, right, dst)
+// level by level.  Returns the slot of the root.
+template <typename Emit>
+static uint32_t batch_merge_schedule(int height, size_t k, const uint64_t* leaf_idx, size_t S, const BatchSib* sibs, uint32_t leaf_slot, uint32_t sib_slot,
+                                     uint32_t& next_slot, Emit emit) {
+    std::vector<size_t> level_first((size_t)height + 1, 0);               // first plan entry of each level
+    for (size_t i = S; i-- > 0;) level_first[sibs[i].level] = i;        // (a level's siblings are contiguous in either sibling order)
+    std::vector<std::pair<uint64_t, uint32_t>> cur(k), nxt;
+    for (size_t i = 0; i < k; i++) cur[i] = {leaf_idx[i], leaf_slot + (uint32_t)i};
+    for (int L = 0; L < height; L++) {
+        nxt.clear();
+        size_t sp = level_first[L];
+        for (size_t i = 0; i < cur.size();) {
+            uint64_t x = cur[i].first;
+            uint32_t left, right;
+            if (!(x & 1) && i + 1 < cur.size() && cur[i + 1].first == x + 1) {
+                left = cur[i].second; right = cur[i + 1].second;
+                i += 2;
+            } else {
+                uint32_t sib = sib_slot + (uint32_t)sp++;
+                if (x & 1) { left = sib; right = cur[i].second; }
+                else { left = cur[i].second; right = sib; }
+                i += 1;
+            }
+            emit(L, left, right, next_slot);
+            nxt.push_back({x >> 1, next_slot});
+            next_slot++;
+        }
+        cur.swap(nxt);
+    }
+    return cur[0].second;
+}
 template <int HW, int DX>
 __global__ void k_batch_merge(int dg, size_t n, const MergeOp* ops, uint32_t* C, uint32_t* Hh, uint32_t* bad) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -183,36 +216,13 @@ int32_t dapol_verify_batch(dapol_ctx* ctx, int32_t height, size_t k, const uint6
     size_t words = 0;
     int max_m = 1;
     if (int32_t rc = batch_policy_plan(ctx, S, policy, aggregation_factor, n_bits, plan, words, &max_m)) return rc;
-    // merge schedule: walk the levels bottom-up; sibling slots are consumed in plan order within their level
-    std::vector<size_t> level_first((size_t)height + 1, 0);               // first plan entry of each level
-    for (size_t i = S; i-- > 0;) level_first[sibs[i].level] = i;        // (a level's siblings are contiguous in either sibling order)
     std::vector<MergeOp> ops;
-    std::vector<size_t> level_ops;                                        // ops.size() after each level
-    std::vector<std::pair<uint64_t, uint32_t>> cur(k), nxt;
-    for (size_t i = 0; i < k; i++) cur[i] = {leaf_idx[i], (uint32_t)i};
+    std::vector<size_t> level_ops((size_t)height, 0);                     // ops.size() after each level
     uint32_t next_slot = (uint32_t)(k + S);
-    for (int L = 0; L < height; L++) {
-        nxt.clear();
-        size_t sp = level_first[L];
-        for (size_t i = 0; i < cur.size();) {
-            uint64_t x = cur[i].first;
-            uint32_t left, right;
-            if (!(x & 1) && i + 1 < cur.size() && cur[i + 1].first == x + 1) {
-                left = cur[i].second; right = cur[i + 1].second;
-                i += 2;
-            } else {
-                uint32_t sib = (uint32_t)(k + sp++);
-                if (x & 1) { left = sib; right = cur[i].second; }
-                else { left = cur[i].second; right = sib; }
-                i += 1;
-            }
-            ops.push_back({left, right, next_slot});
-            nxt.push_back({x >> 1, next_slot});
-            next_slot++;
-        }
-        level_ops.push_back(ops.size());
-        cur.swap(nxt);
-    }
+    batch_merge_schedule(height, k, leaf_idx, S, sibs.data(), 0u, (uint32_t)k, next_slot, [&](int L, uint32_t left, uint32_t right, uint32_t dst) {
+        ops.push_back({left, right, dst});
+        level_ops[L] = ops.size();
+    });
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t slots = next_slot, hw = (size_t)ctx_hw(ctx), hb = hw * 4;

@@ -61,7 +61,8 @@ struct PolicyLanes {
 // draws, same bytes, one pipeline of full launches instead of k part-filled ones (round 6; DAPOL_NO_GROUP=1 proves them one by one).
 static int32_t prove_policy_device(dapol_ctx* ctx, const std::vector<SubProof>& plan, size_t b, int H, const uint64_t* pv, const uint32_t* pr,
                                    const uint32_t* pC, int n_bits, const uint32_t* d_seed, const uint64_t* d_stream, uint32_t* d_range,
-                                   MsmTiming* tm, const uint32_t* d_tape = nullptr /* [b][tape_slots][16]: tape mode */, size_t tape_slots = 0) {
+                                   MsmTiming* tm, const uint32_t* d_tape = nullptr /* [b][tape_slots][16]: tape mode */, size_t tape_slots = 0,
+                                   uint32_t seed_stride = 0 /* words between the rows' seeds in d_seed; 0: one seed for the call */) {
     hipStream_t st = ctx->stream;
     const PolicyGroups PG = group_policy_plan(plan, policy_grouping_on());
     const std::vector<PolicyGroup>& groups = PG.groups;
@@ -96,7 +97,7 @@ static int32_t prove_policy_device(dapol_ctx* ctx, const std::vector<SubProof>& 
         const PolicyLayout::Group& lg = L.g[gi];
         return range_prove_device(lane, n_bits, g.m, b * (size_t)g.k, vals.p + lg.party_off, blind.p + lg.party_off * 8, Vc.p + lg.party_off * 8, d_seed, d_stream,
                                   lg.slot_base, d_tape ? d_tape + lg.slot_base * 16 : nullptr, d_range + lg.word_off, t, tape_slots, (uint32_t)g.k, L.entity_words,
-                                  pend);
+                                  pend, seed_stride);
     };
     int32_t rc = DAPOL_OK;
     if (!on_lanes) {                                         // one group after the other: each call returns after its kernels have drained

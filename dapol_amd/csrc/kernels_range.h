@@ -35,7 +35,8 @@ struct RangeArgs {
     const uint32_t* blind;      // [B][m][8]   integers < 2^255 (reduced on load)
     const uint32_t* Vc;         // [B][m][8]   compressed value commitments
     // nonce source
-    const uint32_t* seed;       // [8] device
+    const uint32_t* seed;       // [8] device; row e's seed at seed + e * seed_stride
+    uint32_t seed_stride;       // words between the rows' seeds: 0 = one seed for the call (every call but dapol_prove_batches)
     // Which proof is chunk-local proof b?  A call proves `sub_k` equal-sized sub-proofs per ROW (an entity of a policy's plan: its
     // individual proofs, or the equal parts of a split -- src/range/padding.rs:104-112, splitting.rs:110-123; 1 for a lone proof per
     // row): proof g = p0 + b of the call is sub-proof j = g % sub_k of row e = g / sub_k (proof_row below).  The row owns the RNG
@@ -117,9 +118,10 @@ __global__ __launch_bounds__(64) void k_rp_nonce_key(RangeArgs A) {
     size_t b = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= A.B || A.tape) return;
     uint32_t key[8], w[16];
-    for (int i = 0; i < 8; i++) key[i] = A.seed[i];
     size_t e; uint32_t sj;
     proof_row(A, b, e, sj);
+    const uint32_t* seed = A.seed + e * (size_t)A.seed_stride;
+    for (int i = 0; i < 8; i++) key[i] = seed[i];
     seed_wide(w, key, 6u, A.stream_id[e], A.slot_base + (uint64_t)sj * A.sub_slots);
     for (int i = 0; i < 8; i++) key[i] = w[i];
     seed_wide(w, key, 7u, (uint64_t)A.n, (uint64_t)A.m);

@@ -245,6 +245,43 @@ struct DapolBatchProof {
                                          root.hash.data(), (int)policy, (int)aggregation_factor, n_bits, range_proofs.data(), range_proofs.size(), verify_seed, &ok));
         return ok != 0;
     }
+    // verify_batch for MANY proofs in one call (dapol_verify_batches): out[j] is what proofs[j].verify_batch(ctx, root, leaves[j]) returns.
+    // One call has one shape: a proof whose height, policy, aggregation factor or bit size differs from proofs[0]'s, or whose leaves do
+    // not number its leaf indexes, is reported invalid and never changes another proof's verdict.  32-byte digests only.
+    static std::vector<bool> verify_many(const Context& ctx, const DapolProofNode& root, const std::vector<DapolBatchProof>& proofs,
+                                         const std::vector<std::vector<DapolProofNode>>& leaves, const uint8_t* verify_seed = nullptr) {
+        if (leaves.size() != proofs.size()) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        std::vector<bool> out(proofs.size(), false);
+        if (proofs.empty()) return out;
+        const DapolBatchProof& f = proofs[0];
+        std::vector<size_t> rows;
+        std::vector<uint64_t> boff{0}, soff{0}, roff{0}, idx;
+        std::vector<uint8_t> lC, lH, sC, sH, blob;
+        auto put = [](std::vector<uint8_t>& to, const Bytes32& b) { to.insert(to.end(), b.begin(), b.end()); };
+        for (size_t j = 0; j < proofs.size(); j++) {
+            const DapolBatchProof& p = proofs[j];
+            if (p.height != f.height || p.policy != f.policy || p.aggregation_factor != f.aggregation_factor || p.n_bits != f.n_bits ||
+                leaves[j].size() != p.leaf_indexes.size())
+                continue;
+            rows.push_back(j);
+            idx.insert(idx.end(), p.leaf_indexes.begin(), p.leaf_indexes.end());
+            for (auto& l : leaves[j]) { put(lC, l.com); put(lH, l.hash); }
+            for (auto& s : p.merkle_siblings) { put(sC, s.com); put(sH, s.hash); }
+            blob.insert(blob.end(), p.range_proofs.begin(), p.range_proofs.end());
+            boff.push_back(idx.size()); soff.push_back(sC.size() / 32); roff.push_back(blob.size());
+        }
+        std::vector<uint8_t> ok(rows.size() + 1, 0);
+        lC.push_back(0); lH.push_back(0); sC.push_back(0); sH.push_back(0); blob.push_back(0); idx.push_back(0);      // (never NULL)
+        check(dapol_verify_batches(ctx.get(), f.height, rows.size(), boff.data(), idx.data(), lC.data(), lH.data(), soff.data(), sC.data(), sH.data(),
+                                   root.com.data(), root.hash.data(), (int)f.policy, (int)f.aggregation_factor, f.n_bits, roff.data(), blob.data(), verify_seed,
+                                   ok.data()));
+        for (size_t i = 0; i < rows.size(); i++) out[rows[i]] = ok[i] != 0;
+        return out;
+    }
+    static std::vector<bool> verify_many(const Context& ctx, const DapolProofNode& root, const std::vector<DapolBatchProof>& proofs,
+                                         const std::vector<std::vector<DapolProofNode>>& leaves, const Bytes32& verify_seed) {
+        return verify_many(ctx, root, proofs, leaves, verify_seed.data());
+    }
 };
 
 // LiabilityId / Liability / DapolOptions (src/dapol/mod.rs:36-56)
@@ -393,6 +430,18 @@ class Dapol {
             idx.push_back(it->second);
         }
         return generate_proof_batch(idx, nonce_seed, n_bits);
+    }
+    // generate_proof_batch_for_ids for many lists of ids in one call (generate_proof_batches): None when one id is unknown.
+    std::optional<std::vector<DapolBatchProof>> generate_proof_batches_for_ids(const std::vector<std::vector<LiabilityId>>& ids, const Bytes32& nonce_seed,
+                                                                               int n_bits = 64) const {
+        std::vector<std::vector<uint64_t>> batches(ids.size());
+        for (size_t j = 0; j < ids.size(); j++)
+            for (auto& id : ids[j]) {
+                auto it = id_to_idx_map_.find(id);
+                if (it == id_to_idx_map_.end()) return std::nullopt;
+                batches[j].push_back(it->second);
+            }
+        return generate_proof_batches(batches, nonce_seed, n_bits);
     }
     const std::map<LiabilityId, uint64_t>& id_to_idx_map() const { return id_to_idx_map_; }
     // Dapol::new_blank (mod.rs:196-204)
@@ -557,6 +606,35 @@ class Dapol {
             std::memcpy(out.merkle_siblings[s].hash.data(), &H[s * 32], 32);
         }
         out.policy = policy_; out.aggregation_factor = aggregation_factor_; out.n_bits = n_bits; out.height = height_;
+        return out;
+    }
+    // generate_proof_batch for MANY lists of leaves in one GPU call (dapol_prove_batches): out[j] equals generate_proof_batch(batches[j])
+    // under the same seed, byte for byte; batches may overlap and repeat.  None when there is no liability at one of the leaves.
+    std::optional<std::vector<DapolBatchProof>> generate_proof_batches(const std::vector<std::vector<uint64_t>>& batches, const Bytes32& nonce_seed,
+                                                                       int n_bits = 64) const {
+        const size_t nb = batches.size();
+        std::vector<uint64_t> boff{0}, idx;
+        for (auto& b : batches) { idx.insert(idx.end(), b.begin(), b.end()); boff.push_back(idx.size()); }
+        idx.push_back(0);                                             // (never NULL)
+        std::vector<uint64_t> soff(nb + 1), roff(nb + 1);
+        check(dapol_batches_plan(height_, nb, boff.data(), idx.data(), (int)policy_, (int)aggregation_factor_, n_bits, nullptr, soff.data(), roff.data(), nullptr));
+        std::vector<uint8_t> C(soff[nb] * 32 + 1), H(soff[nb] * 32 + 1), blob(roff[nb] + 1);
+        int32_t rc = dapol_prove_batches(ctx_->get(), tree_.get(), nb, boff.data(), idx.data(), (int)policy_, (int)aggregation_factor_, n_bits, nonce_seed.data(),
+                                         C.data(), H.data(), blob.data(), nullptr);
+        if (rc == DAPOL_ERR_UNKNOWN_LEAF) return std::nullopt;
+        check(rc);
+        std::vector<DapolBatchProof> out(nb);
+        for (size_t j = 0; j < nb; j++) {
+            DapolBatchProof& p = out[j];
+            p.leaf_indexes = batches[j];
+            p.merkle_siblings.resize(soff[j + 1] - soff[j]);
+            for (size_t s = 0; s < p.merkle_siblings.size(); s++) {
+                std::memcpy(p.merkle_siblings[s].com.data(), &C[(soff[j] + s) * 32], 32);
+                std::memcpy(p.merkle_siblings[s].hash.data(), &H[(soff[j] + s) * 32], 32);
+            }
+            p.range_proofs.assign(blob.begin() + roff[j], blob.begin() + roff[j + 1]);
+            p.policy = policy_; p.aggregation_factor = aggregation_factor_; p.n_bits = n_bits; p.height = height_;
+        }
         return out;
     }
     // Many single-leaf proofs in one GPU batch (the throughput path).

@@ -630,6 +630,48 @@ int32_t dapol_verify_batch_checked(dapol_ctx* ctx, int32_t height, size_t k, con
                                    int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint8_t* range_proofs, size_t range_proofs_len,
                                    const uint8_t verify_seed32[32], uint8_t* ok);
 
+/* MANY batched inclusion proofs in one call -- Dapol::generate_proof_batch_for_ids (src/dapol/mod.rs:155-190) for every customer
+ * who holds several accounts, or for every sample of an auditor: nb batches, batch j = the leaves
+ * leaf_idx[batch_off[j] .. batch_off[j + 1]) (batch_off[0] = 0).  Every batch is non-empty, strictly increasing and below 2^height;
+ * batches may overlap each other and may repeat.
+ *   Definition.  The prover's outputs are the concatenation, in the caller's batch order, of what dapol_prove_batch returns for
+ * each batch under the same nonce_seed32 -- siblings and range blobs, byte for byte: batch j's siblings are records
+ * [sib_off[j], sib_off[j + 1]) of sib_C32 / sib_H32 and its blob is bytes [range_off[j], range_off[j + 1]) of range_out, at
+ * dapol_batches_plan's offsets.  So a batch of one leaf is proved under the caller's seed (dapol_prove_entities' bytes), a longer one
+ * under the seed chained through its leaves, with its first leaf as the stream id.  ok[j] of the verifier is what
+ * dapol_verify_batch_checked returns for batch j, for every input.
+ *   How.  A batch with S deduplicated siblings is one row of the policy prover over S siblings, and the batches of a call with
+ * equal S share one plan: each distinct S is ONE [rows][S] call of the batched prover (verifier) instead of one small call per
+ * batch.  The groups run one after the other; *n_groups_out (may be NULL) is their number.  A call with few distinct S is fast; a
+ * call whose every batch has an S of its own does what a loop over dapol_prove_batch does.
+ *   dapol_batches_plan: host-only (no context, no GPU).  Each output may be NULL: n_siblings [nb], sib_off [nb + 1] in sibling
+ * records, range_off [nb + 1] in bytes (dapol_entity_proof_size(n_siblings[j], policy, aggregation_factor, n_bits) each), *n_groups.
+ * Honours dapol_wire_config.siblings_leaf_first.  Refusals: height > 64 -> DAPOL_ERR_TREE_HEIGHT_TOO_BIG; a batch_off that does
+ * not start at 0 or decreases, or leaves x height >= 2^32 (the gather index has 32 bits) -> DAPOL_ERR_INVALID_ARGUMENT; then
+ * dapol_prove_batch's refusals (bad leaf indexes, aggregation_factor outside [0, n_siblings[j]], a bad n_bits) for the FIRST batch in
+ * caller order that it would refuse, with "batch <j>:" in dapol_last_error.  nb = 0 is DAPOL_OK with empty outputs.
+ *   dapol_prove_batches: everything is validated on the host before anything is queued.  sib_C32 / sib_H32 (may be NULL):
+ * [sib_off[nb]][32]; range_out: range_off[nb] bytes.  A leaf that the tree does not hold -> DAPOL_ERR_UNKNOWN_LEAF with no output
+ * written; a shard tree is refused as dapol_prove_batch refuses it.
+ *   dapol_verify_batches: leaf_C32 / leaf_H32 [batch_off[nb]][32]; sib_off [nb + 1] and range_off [nb + 1] are the lengths the caller
+ * actually HOLDS (records of sib_C32 / sib_H32, bytes of range_proofs; non-decreasing, else DAPOL_ERR_INVALID_ARGUMENT): a batch
+ * whose counts differ from the plan's is an invalid proof -- ok[j] = 0 -- not an error and never an over-read, and it never changes
+ * another batch's verdict.  Errors are dapol_verify_batch_checked's, for the first batch in caller order.  verify_seed32 = NULL
+ * draws a seed from the OS.  Only ok[nb] comes back from the device.
+ *   Left out: 64-byte digests (a Blake2b context is refused with DAPOL_ERR_INVALID_DIGEST_SIZE by both calls), shard trees and the
+ * records route, tape mode, S-groups side by side, sub-proofs shared between batches. */
+int32_t dapol_batches_plan(int32_t height, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx, int32_t policy,
+                           int32_t aggregation_factor, int32_t n_bits, uint64_t* n_siblings, uint64_t* sib_off, uint64_t* range_off,
+                           uint64_t* n_groups);
+int32_t dapol_prove_batches(dapol_ctx* ctx, dapol_tree* tree, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx,
+                            int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint8_t nonce_seed32[32], uint8_t* sib_C32,
+                            uint8_t* sib_H32, uint8_t* range_out, uint64_t* n_groups_out);
+int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx,
+                             const uint8_t* leaf_C32, const uint8_t* leaf_H32, const uint64_t* sib_off, const uint8_t* sib_C32,
+                             const uint8_t* sib_H32, const uint8_t root_C32[32], const uint8_t root_H32[32], int32_t policy,
+                             int32_t aggregation_factor, int32_t n_bits, const uint64_t* range_off, const uint8_t* range_proofs,
+                             const uint8_t verify_seed32[32], uint8_t* ok);
+
 /* SHARED sub-proofs on the verifier's side -- the counterpart of dapol_prove_entities_shared: a call that checks many entities'
  * proofs (an exchange before it publishes them, an auditor who checks everyone's) verifies every run of equal sub-proofs once.
  * Arguments, refusals and error codes as dapol_verify_entities_checked / dapol_verify_entities (shared or per-entity blobs, decoded
