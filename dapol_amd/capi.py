@@ -120,6 +120,10 @@ _SIG = {
     "dapol_prove_batches": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "dapol_verify_batches": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, _P, _P, _P, _P]),
+    "dapol_reprove_batches_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_int32, _P, _P, _P, _P]),
+    "dapol_reprove_batches": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P,
+                                               _P, _P, _P]),
     "dapol_entity_proof_size": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "dapol_prove_entities_upper": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
                                                     _P, _P, _P, _P, _P, _P, _P]),
@@ -601,6 +605,20 @@ def batches_plan(height, batches, policy, aggregation_factor, n_bits):
     return ns, so, ro, int(ng.value)
 
 
+def reprove_batches_plan(height, batches, edited_idx, policy, aggregation_factor, n_bits, has_old=None):
+    """dapol_reprove_batches_plan (host-only): what Tree.reprove_batches would prove after the leaves `edited_idx` (replaced, inserted
+    and removed ones, strictly increasing) changed: (dirty sub-proofs per batch [nb], their sum, the sum of m over them, the sum of m
+    over every sub-proof of the call).  has_old[j] = 0 marks a batch without an old proof."""
+    nb, off, flat = _pack_batches(batches)
+    edited_idx = _u64(edited_idx)
+    ho = None if has_old is None else _u8(has_old, nb)
+    n_proved = np.zeros(nb, np.uint64)
+    tot, sm, sm_all = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _chk(lib().dapol_reprove_batches_plan(height, nb, _ptr(off), _ptr(flat), _ptr(ho), edited_idx.shape[0], _ptr(edited_idx), policy, aggregation_factor,
+                                          n_bits, _ptr(n_proved), ctypes.byref(tot), ctypes.byref(sm), ctypes.byref(sm_all)))
+    return n_proved, int(tot.value), int(sm.value), int(sm_all.value)
+
+
 def shared_plan(height, leaf_idx, policy, aggregation_factor):
     """dapol_shared_plan (host-only): (distinct subtree keys per sub-proof of the plan, their sum = range proofs that
     prove_entities_shared computes, b x plan size = what prove_entities computes).  height = siblings per entity."""
@@ -994,6 +1012,29 @@ class Tree:
         _chk(lib().dapol_prove_batches(self.ctx.h, self.h, nb, _ptr(off), _ptr(flat), policy, aggregation_factor, n_bits, _ptr(seed), _ptr(C), _ptr(H),
                                        _ptr(out), ctypes.byref(ng)))
         return so, ro, C, H, out, int(ng.value)
+
+    def reprove_batches(self, batches, old_sib_C, old_range, policy, aggregation_factor, n_bits, nonce_seed, has_old=None, alias=False):
+        """dapol_reprove_batches: prove_batches' outputs for the tree as it is now, proving only the sub-proofs whose sibling
+        commitments differ from old_sib_C [sib_off[nb]][32]; the others keep their bytes of old_range [range_off[nb]] (both in
+        batches_plan's layout; None: no old data, which needs has_old all zero).  has_old[j] = 0 marks a batch without an old proof.
+        alias=True writes the commitments and the blobs into the old arrays themselves (which must be writable, contiguous uint8).
+        Returns prove_batches' tuple with (proved, kept, n_calls) in place of the S-groups: (sib_off, range_off, sib_C, sib_H, range
+        bytes, proved, kept, n_calls)."""
+        nb, off, flat = _pack_batches(batches)
+        _, so, ro, _ = batches_plan(self.height, batches, policy, aggregation_factor, n_bits)
+        T, R = int(so[-1]), int(ro[-1])
+        oC = None if old_sib_C is None else _u8(old_sib_C, T, 32)
+        oR = None if old_range is None else _u8(old_range, R)
+        ho = None if has_old is None else _u8(has_old, nb)
+        H = np.zeros((T, 32), np.uint8)
+        if alias and (oC is None or oR is None or not np.shares_memory(oC, old_sib_C) or not np.shares_memory(oR, old_range)):
+            raise DapolError(8, "alias=True needs old arrays that are contiguous uint8 numpy arrays")
+        C, out = (oC, oR) if alias else (np.zeros((T, 32), np.uint8), np.zeros(R, np.uint8))
+        seed = _u8(np.frombuffer(nonce_seed, np.uint8))
+        proved, kept, calls = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _chk(lib().dapol_reprove_batches(self.ctx.h, self.h, nb, _ptr(off), _ptr(flat), policy, aggregation_factor, n_bits, _ptr(seed), _ptr(ho), _ptr(oC),
+                                         _ptr(oR), _ptr(C), _ptr(H), _ptr(out), ctypes.byref(proved), ctypes.byref(kept), ctypes.byref(calls)))
+        return so, ro, C, H, out, int(proved.value), int(kept.value), int(calls.value)
 
     def prove_entities(self, leaf_idx, policy, aggregation_factor, n_bits, nonce_seed, upper=None, tape=None):
         """upper = (C[u,32], H[u,32], v[u], r[u,32]) siblings above a shard root, root side first.

@@ -25,6 +25,7 @@
 #include "kernels_store.h"
 #include "kernels_compact_paths.h"
 #include "kernels_batches.h"
+#include "kernels_reprove_batches.h"
 
 using namespace dapol;
 
@@ -490,4 +491,5 @@ int32_t dapol_commit_hash_batch(dapol_ctx* ctx, size_t n, const uint64_t* v, con
 #include "host_wire.inc"
 #include "host_batch.inc"
 #include "host_batches.inc"
+#include "host_reprove_batches.inc"
 #include "host_comm.inc"

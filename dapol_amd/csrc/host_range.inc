@@ -341,7 +341,8 @@ static int32_t queue_chunk(dapol_ctx* ctx, const ProvePlan& P, const ProveLane& 
 static int32_t range_prove_device(dapol_ctx* ctx, int n, int m, size_t B, const uint64_t* d_vals, const uint32_t* d_blind,
                                   const uint32_t* d_Vc, const uint32_t* d_seed, const uint64_t* d_stream, uint64_t slot_base,
                                   const uint32_t* d_tape, uint32_t* d_out, MsmTiming* tm, size_t tape_stride = 0, uint32_t sub_k = 1,
-                                  size_t out_stride = 0, PendingProve* pend = nullptr, uint32_t seed_stride = 0 /* words; 0: one seed */) {
+                                  size_t out_stride = 0, PendingProve* pend = nullptr, uint32_t seed_stride = 0 /* words; 0: one seed */,
+                                  const uint64_t* d_slot_of = nullptr /* [B] first slot of every proof (RangeArgs::slot_of); null: slot_base */) {
     ProveShape s{};
     s.n = n; s.m = m; s.B = B;
     s.tail_length = ctx->opt.tail_length; s.small_call_max = ctx->opt.small_call_max; s.generator_stationary = ctx->opt.generator_stationary;
@@ -369,7 +370,7 @@ static int32_t range_prove_device(dapol_ctx* ctx, int n, int m, size_t B, const 
     RangeArgs A{};                                           // what every chunk of the call shares
     A.n = n; A.m = m; A.N = P.N; A.lgN = P.lgN; A.TP = P.TP;
     A.out_words = 72 + 16 * A.lgN;
-    A.seed = d_seed; A.seed_stride = seed_stride; A.slot_base = slot_base;
+    A.seed = d_seed; A.seed_stride = seed_stride; A.slot_base = slot_base; A.slot_of = d_slot_of;
     A.wbits = s.wbits; A.nwin = s.nwin;
     A.prep = (P.prep_recode ? PREP_RECODE : 0) | (P.prep_share ? PREP_SHARE : 0);
     A.tail_n = P.tail_n; A.use_hi = P.use_hi ? 1 : 0; A.fs_parts = P.fs_parts; A.mat_round = P.nf_rounds();

@@ -43,6 +43,7 @@ struct RangeArgs {
     // stream and the tape row; the sub-proof's draws start sub_slots = m(2n+4) after its predecessor's.
     const uint64_t* stream_id;  // [rows] of the CALL (not of the chunk)
     uint64_t slot_base;         // first slot of sub-proof 0
+    const uint64_t* slot_of;    // null, or [proofs] of the CALL: proof p0 + b draws from slot_of[p0 + b] on, not from slot_base + j * sub_slots (dapol_reprove_batches)
     const uint32_t* tape;       // [rows][tape_stride][16] or null; sub-proof 0's slots start at the pointer
     uint32_t tape_stride;       // draws per row in `tape`: m(2n+4) for a lone proof, the whole entity's slots when the sub-proofs of a policy share one stream
     uint32_t sub_k, sub_slots;
@@ -106,7 +107,7 @@ __device__ __forceinline__ void tape_wide(uint32_t* w16, const RangeArgs& A, siz
     } else {
         uint32_t key[8];
         for (int i = 0; i < 8; i++) key[i] = A.st[b].nkey[i];
-        seed_wide(w16, key, 2u, A.stream_id[e], A.slot_base + first + slot);
+        seed_wide(w16, key, 2u, A.stream_id[e], (A.slot_of ? A.slot_of[A.p0 + b] : A.slot_base + first) + slot);
     }
 }
 // Seed mode: the key of one proof's nonce stream.  The reference's prover draws fresh thread_rng randomness on every call;
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(64) void k_rp_nonce_key(RangeArgs A) {
     proof_row(A, b, e, sj);
     const uint32_t* seed = A.seed + e * (size_t)A.seed_stride;
     for (int i = 0; i < 8; i++) key[i] = seed[i];
-    seed_wide(w, key, 6u, A.stream_id[e], A.slot_base + (uint64_t)sj * A.sub_slots);
+    seed_wide(w, key, 6u, A.stream_id[e], A.slot_of ? A.slot_of[A.p0 + b] : A.slot_base + (uint64_t)sj * A.sub_slots);
     for (int i = 0; i < 8; i++) key[i] = w[i];
     seed_wide(w, key, 7u, (uint64_t)A.n, (uint64_t)A.m);
     for (int i = 0; i < 8; i++) key[i] = w[i];

@@ -637,6 +637,71 @@ class Dapol {
         }
         return out;
     }
+    // After update / insert / remove / apply: generate_proof_batches' proofs for the tree as it is now, proving only the sub-proofs whose
+    // sibling commitments moved (dapol_reprove_batches) and keeping the bytes of the others.  out[j] is the proof for
+    // old_proofs[j].leaf_indexes: the caller drops the proofs of batches that lost a leaf, and passes a DapolBatchProof with only its
+    // leaf_indexes set for a batch that is new -- an old proof that is not of this Dapol's shape (height, policy, aggregation factor,
+    // n_bits, sibling count, blob length) is proved from scratch.  Returns the proofs and the number of range proofs actually computed;
+    // None when there is no liability at one of the leaves.  With old proofs from generate_proof_batches (or generate_proof_batch)
+    // under the same nonce_seed the result equals generate_proof_batches' byte for byte.  Old bytes are not checked:
+    // DapolBatchProof::verify_batch is the check.
+    std::optional<std::pair<std::vector<DapolBatchProof>, uint64_t>> regenerate_proof_batches(const std::vector<DapolBatchProof>& old_proofs,
+                                                                                             const Bytes32& nonce_seed, int n_bits = 64) const {
+        const size_t nb = old_proofs.size();
+        std::vector<uint64_t> boff{0}, idx;
+        for (auto& p : old_proofs) { idx.insert(idx.end(), p.leaf_indexes.begin(), p.leaf_indexes.end()); boff.push_back(idx.size()); }
+        idx.push_back(0);                                             // (never NULL)
+        std::vector<uint64_t> soff(nb + 1), roff(nb + 1);
+        check(dapol_batches_plan(height_, nb, boff.data(), idx.data(), (int)policy_, (int)aggregation_factor_, n_bits, nullptr, soff.data(), roff.data(), nullptr));
+        std::vector<uint8_t> has_old(nb + 1, 0), oldC(soff[nb] * 32 + 1, 0), oldR(roff[nb] + 1, 0), C(soff[nb] * 32 + 1), H(soff[nb] * 32 + 1), blob(roff[nb] + 1);
+        for (size_t j = 0; j < nb; j++) {
+            const DapolBatchProof& p = old_proofs[j];
+            if (p.height != height_ || p.policy != policy_ || p.aggregation_factor != aggregation_factor_ || p.n_bits != n_bits ||
+                p.merkle_siblings.size() != soff[j + 1] - soff[j] || p.range_proofs.size() != roff[j + 1] - roff[j])
+                continue;
+            has_old[j] = 1;
+            for (size_t s = 0; s < p.merkle_siblings.size(); s++) std::memcpy(&oldC[(soff[j] + s) * 32], p.merkle_siblings[s].com.data(), 32);
+            if (!p.range_proofs.empty()) std::memcpy(&oldR[roff[j]], p.range_proofs.data(), p.range_proofs.size());
+        }
+        uint64_t proved = 0;
+        int32_t rc = dapol_reprove_batches(ctx_->get(), tree_.get(), nb, boff.data(), idx.data(), (int)policy_, (int)aggregation_factor_, n_bits, nonce_seed.data(),
+                                           has_old.data(), oldC.data(), oldR.data(), C.data(), H.data(), blob.data(), &proved, nullptr, nullptr);
+        if (rc == DAPOL_ERR_UNKNOWN_LEAF) return std::nullopt;
+        check(rc);
+        std::vector<DapolBatchProof> out(nb);
+        for (size_t j = 0; j < nb; j++) {
+            DapolBatchProof& p = out[j];
+            p.leaf_indexes = old_proofs[j].leaf_indexes;
+            p.merkle_siblings.resize(soff[j + 1] - soff[j]);
+            for (size_t s = 0; s < p.merkle_siblings.size(); s++) {
+                std::memcpy(p.merkle_siblings[s].com.data(), &C[(soff[j] + s) * 32], 32);
+                std::memcpy(p.merkle_siblings[s].hash.data(), &H[(soff[j] + s) * 32], 32);
+            }
+            p.range_proofs.assign(blob.begin() + roff[j], blob.begin() + roff[j + 1]);
+            p.policy = policy_; p.aggregation_factor = aggregation_factor_; p.n_bits = n_bits; p.height = height_;
+        }
+        return std::make_pair(std::move(out), proved);
+    }
+    // What regenerate_proof_batches would prove after the leaves `edited` (strictly increasing: replaced, inserted and removed ones)
+    // changed, without a GPU call (dapol_reprove_batches_plan).  has_old: empty = every batch has an old proof, else one flag per batch.
+    struct BatchesReprovePlan {
+        std::vector<uint64_t> proved_per_batch;          // dirty sub-proofs of each batch
+        uint64_t proved = 0, sum_m_proved = 0, sum_m_all = 0;
+    };
+    BatchesReprovePlan regenerate_proof_batches_plan(const std::vector<std::vector<uint64_t>>& batches, const std::vector<uint64_t>& edited,
+                                                     const std::vector<uint8_t>& has_old = {}, int n_bits = 64) const {
+        const size_t nb = batches.size();
+        if (!has_old.empty() && has_old.size() != nb) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+        std::vector<uint64_t> boff{0}, idx;
+        for (auto& b : batches) { idx.insert(idx.end(), b.begin(), b.end()); boff.push_back(idx.size()); }
+        idx.push_back(0);                                             // (never NULL)
+        BatchesReprovePlan out;
+        out.proved_per_batch.assign(nb + 1, 0);
+        check(dapol_reprove_batches_plan(height_, nb, boff.data(), idx.data(), has_old.empty() ? nullptr : has_old.data(), edited.size(), edited.data(),
+                                         (int)policy_, (int)aggregation_factor_, n_bits, out.proved_per_batch.data(), &out.proved, &out.sum_m_proved, &out.sum_m_all));
+        out.proved_per_batch.resize(nb);
+        return out;
+    }
     // Many single-leaf proofs in one GPU batch (the throughput path).
     std::optional<std::vector<DapolProof>> generate_proofs(const std::vector<uint64_t>& leaves, const Bytes32& nonce_seed, int n_bits = 64) const {
         return prove_many(leaves, nonce_seed, n_bits, false);

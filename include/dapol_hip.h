@@ -672,6 +672,57 @@ int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const ui
                              int32_t aggregation_factor, int32_t n_bits, const uint64_t* range_off, const uint8_t* range_proofs,
                              const uint8_t verify_seed32[32], uint8_t* ok);
 
+/* RE-PROVING BATCHES after an edit of the tree (dapol_tree_update / _insert / _remove / _apply) -- what dapol_reprove_entities_shared
+ * is to single-leaf proofs.  A sub-proof {start, count, m} of a batch is a statement about `count` sibling commitments, and its nonce
+ * key is derived from the batch's seed (the caller's for one leaf, the chain through the leaves otherwise), the stream id (the
+ * batch's first leaf), the sub-proof's first slot (a function of the plan alone), (n, m) and those commitments -- from nothing else.
+ * So a sub-proof whose sibling commitments did not move has exactly the bytes it had, and one whose commitments moved gets fresh
+ * nonces.  dapol_reprove_batches takes the caller's old siblings and blobs and proves only what moved.
+ *   Arguments.  The batches are dapol_prove_batches': non-empty, strictly increasing, free to overlap and repeat, and leaves of the
+ * tree AS IT IS NOW (the caller drops the batches that lost a leaf).  The offsets are dapol_batches_plan's sib_off / range_off:
+ * sibling positions depend on the batch's leaves alone, so no edit moves them.  old_sib_C32 [sib_off[nb]][32] and old_range
+ * (range_off[nb] bytes) are in that layout.  has_old[j] = 0 marks a batch with no old proof, whose old rows are ignored;
+ * has_old = NULL: every batch has an old proof.
+ *   Definitions.  DIRTY(j, s): has_old[j] == 0, or the `count` commitments old_sib_C32[sib_off[j] + start .. + count) differ in any
+ * byte from the tree's current ones -- a comparison of bytes: nothing is keyed, no index is trusted.  The siblingless pad proof of
+ * aggregation 0 (count = 0) is dirty only without an old proof.  Every dirty sub-proof is proved with the seed, stream id and slot
+ * that dapol_prove_batch uses for it, its padding parties the policy's (v = 0, r = 1, commitment B_blinding); one that is not dirty
+ * keeps its old bytes.  There is no head rule: batches share nothing, and a repeated batch is proved twice.  *proved_out = dirty
+ * sub-proofs, *kept_out = the other (batch, sub-proof) pairs, *n_calls_out = calls of the range prover made: all dirty sub-proofs
+ * of one m are ONE call whatever their batch's sibling count, so at most the number of distinct m (each may be NULL).
+ *   Consequences.  With old data from dapol_prove_batches or dapol_prove_batch under the same seed, policy, factor, n_bits and
+ * sibling order, the outputs equal a fresh dapol_prove_batches on the edited tree byte for byte.  With another seed the kept pieces
+ * stay valid but differ from a fresh call.  Old bytes are NOT checked: what goes in on a kept sub-proof comes out unchanged --
+ * dapol_verify_batches is the check.  Outputs may alias the old arrays (every input is uploaded before anything is written back).
+ * When nothing is dirty the range prover is not entered.
+ *   Refusals.  What dapol_prove_batches refuses, with its codes, messages ("batch <j>:") and precedence, shard trees and 64-byte
+ * digests included; an unknown leaf -> DAPOL_ERR_UNKNOWN_LEAF with nothing written; after those, a NULL old array (old_sib_C32 while
+ * there are siblings, old_range while there are blob bytes) while some batch has an old proof -> DAPOL_ERR_INVALID_ARGUMENT.
+ * nb = 0 is DAPOL_OK.
+ *   dapol_reprove_batches_plan: host-only index arithmetic (no context, no GPU, no tree).  edited_idx [k]: strictly increasing and
+ * below 2^height (else DAPOL_ERR_INVALID_ARGUMENT, after dapol_batches_plan's own refusals), the replaced, inserted and removed
+ * leaves.  DIRTY(j, s): !has_old[j], or some edited x lies below a sibling of the sub-proof: x >> level == index for one of the
+ * positions dapol_batch_siblings gives.  An edited leaf that is a leaf of the batch lies below none of its siblings and dirties
+ * nothing of that batch.  Exact when every edit really changes its leaf's commitment, an upper bound otherwise.  n_proved [nb] (may
+ * be NULL) = dirty sub-proofs of each batch, *total_proved their sum = what dapol_reprove_batches proves, *sum_m_proved and
+ * *sum_m_all = the sums of m over the dirty sub-proofs and over all of them: one call gives the ratio.
+ *   When to use it (tools/bench_reprove_batches.py): the time follows the sum of m over the dirty sub-proofs
+ * plus the trip of the old arrays, and the call pays one latency chain per distinct m where dapol_prove_batches pays one per distinct
+ * sibling count.  2^16 leaves at height 32, 4,096 batches of 2 / 4 random leaves, 64-bit proofs, one MI355X, whole call against
+ * dapol_prove_batches on the same edited tree, 1 to 4,096 replaced liabilities: padding / 16 0.28 / 0.50 -> 0.07-0.14 s (x3.4-6.5; the
+ * sum-of-m ratio is 2.8-7.7), splitting / 24 0.34 / 0.61 -> 0.07-0.15 s (x3.6-7.1 of 2.5-7.5), padding / 0 0.26 / 0.47 -> 0.02-0.13 s
+ * (x3.3-13 of 2.9-118).  Padding with the factor at the smallest sibling count of the call (51; next to nothing is kept) still ran
+ * in 0.18 s against 0.42 s, because all of its 64-party proofs are one call here and twelve S-groups there.
+ *   Left out: a device-resident store for batch proofs, shard trees and the records route, 64-byte digests, tape mode (DESIGN.md
+ * section 9). */
+int32_t dapol_reprove_batches_plan(int32_t height, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx, const uint8_t* has_old,
+                                   size_t k, const uint64_t* edited_idx, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                                   uint64_t* n_proved, uint64_t* total_proved, uint64_t* sum_m_proved, uint64_t* sum_m_all);
+int32_t dapol_reprove_batches(dapol_ctx* ctx, dapol_tree* tree, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx,
+                              int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint8_t nonce_seed32[32],
+                              const uint8_t* has_old, const uint8_t* old_sib_C32, const uint8_t* old_range, uint8_t* sib_C32,
+                              uint8_t* sib_H32, uint8_t* range_out, uint64_t* proved_out, uint64_t* kept_out, uint64_t* n_calls_out);
+
 /* SHARED sub-proofs on the verifier's side -- the counterpart of dapol_prove_entities_shared: a call that checks many entities'
  * proofs (an exchange before it publishes them, an auditor who checks everyone's) verifies every run of equal sub-proofs once.
  * Arguments, refusals and error codes as dapol_verify_entities_checked / dapol_verify_entities (shared or per-entity blobs, decoded
