@@ -158,6 +158,14 @@ _SIG = {
     "dapol_proof_store_read": (ctypes.c_int32, [_P, ctypes.c_size_t, ctypes.c_size_t, _P, _P, _P, _P]),
     "dapol_proof_store_verify": (ctypes.c_int32, [_P, _P, _P]),
     "dapol_proof_store_read_compact": (ctypes.c_int32, [_P, _P, ctypes.c_size_t, _P]),
+    "dapol_batch_store_create": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.POINTER(_P)]),
+    "dapol_batch_store_destroy": (ctypes.c_int32, [_P]),
+    "dapol_batch_store_refresh": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P]),
+    "dapol_batch_store_rows": (ctypes.c_size_t, [_P]),
+    "dapol_batch_store_layout": (ctypes.c_int32, [_P, _P, _P, _P, _P]),
+    "dapol_batch_store_fetch": (ctypes.c_int32, [_P, ctypes.c_size_t, _P, _P, _P, _P]),
+    "dapol_batch_store_read": (ctypes.c_int32, [_P, ctypes.c_size_t, ctypes.c_size_t, _P, _P, _P]),
+    "dapol_batch_store_verify": (ctypes.c_int32, [_P, _P, _P]),
     "dapol_workload_create": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_create_shard": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(_P)]),
     "dapol_workload_build": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(WorkloadStats)]),
@@ -1200,6 +1208,88 @@ class ProofStore:
         ok = np.zeros(self.rows, np.uint8)
         seed = _u8(np.frombuffer(verify_seed, np.uint8)) if verify_seed is not None else None   # None: the library draws one from the OS
         _chk(lib().dapol_proof_store_verify(self.h, _ptr(seed), _ptr(ok) if ok.shape[0] else None))
+        return ok
+
+
+class BatchStore:
+    """dapol_batch_store: the proofs of prove_batches for one batch list under one (tree, policy, aggregation factor, n_bits, nonce
+    seed), resident in HBM and re-proved in place after edits of the tree.  A row is a batch, in the order of the last refresh.  Keeps
+    a reference to its Tree (which cannot be closed while the store is open)."""
+
+    def __init__(self, tree, policy, aggregation_factor, n_bits, nonce_seed):
+        self.tree, self.ctx = tree, tree.ctx
+        seed = _u8(np.frombuffer(nonce_seed, np.uint8))
+        self.h = _P()
+        _chk(lib().dapol_batch_store_create(tree.ctx.h, tree.h, policy, aggregation_factor, n_bits, _ptr(seed), ctypes.byref(self.h)))
+        self.policy, self.aggregation_factor, self.n_bits = policy, aggregation_factor, n_bits
+
+    def close(self):
+        if self.h:
+            lib().dapol_batch_store_destroy(self.h)
+            self.h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def rows(self):
+        return int(lib().dapol_batch_store_rows(self.h))
+
+    def refresh(self, batches=None):
+        """Makes the store hold prove_batches' proofs of `batches` ([[leaf, ...], ...]; None: the list it already holds; an empty list
+        empties it) for the tree as it is now.  Returns (proved, kept, n_calls, moved_rows)."""
+        proved, kept, calls, moved = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if batches is None:
+            nb, off, flat = 0, None, None
+        else:
+            nb, off, flat = _pack_batches(batches)
+        _chk(lib().dapol_batch_store_refresh(self.h, nb, _ptr(off), _ptr(flat), ctypes.byref(proved), ctypes.byref(kept), ctypes.byref(calls), ctypes.byref(moved)))
+        return int(proved.value), int(kept.value), int(calls.value), int(moved.value)
+
+    def layout(self):
+        """(batches, sib_off [rows + 1] in sibling records, range_off [rows + 1] in bytes): the stored list and batches_plan's offsets."""
+        n = self.rows
+        off, so, ro = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        _chk(lib().dapol_batch_store_layout(self.h, _ptr(off), None, _ptr(so), _ptr(ro)))
+        flat = np.zeros(max(int(off[-1]), 1), np.uint64)
+        _chk(lib().dapol_batch_store_layout(self.h, None, _ptr(flat), None, None))
+        return [flat[int(off[j]):int(off[j + 1])].tolist() for j in range(n)], so, ro
+
+    def fetch(self, rows):
+        """The given rows (any order, duplicates allowed) in batches_plan's layout of those batches in query order:
+        (sib_off [k + 1], range_off [k + 1], sib_C, sib_H, range bytes)."""
+        rows = _u64(rows)
+        k = rows.shape[0]
+        _, so, ro = self.layout()
+        n = so.shape[0] - 1
+        qs, qr = np.zeros(k + 1, np.uint64), np.zeros(k + 1, np.uint64)
+        if k and int(rows.max()) < n:                                           # (else the library refuses the call: nothing to size)
+            r = rows.astype(np.int64)
+            qs[1:], qr[1:] = np.cumsum(so[r + 1] - so[r]), np.cumsum(ro[r + 1] - ro[r])
+        T, R = int(qs[-1]), int(qr[-1])
+        C, H, out = np.zeros((T, 32), np.uint8), np.zeros((T, 32), np.uint8), np.zeros(R, np.uint8)
+        _chk(lib().dapol_batch_store_fetch(self.h, k, _ptr(rows) if k else None, _ptr(C), _ptr(H), _ptr(out)))
+        return qs, qr, C, H, out
+
+    def read(self, first=0, count=None):
+        """Rows [first, first + count) (count None: to the end): (sib_C, sib_H, range bytes), the slices of prove_batches' outputs."""
+        n = self.rows
+        count = n - first if count is None else count
+        _, so, ro = self.layout()
+        lo, hi = min(first, n), min(max(first + count, first), n)
+        T, R = int(so[hi] - so[lo]), int(ro[hi] - ro[lo])
+        C, H, out = np.zeros((T, 32), np.uint8), np.zeros((T, 32), np.uint8), np.zeros(R, np.uint8)
+        _chk(lib().dapol_batch_store_read(self.h, first, count, _ptr(C), _ptr(H), _ptr(out)))
+        return C, H, out
+
+    def verify(self, verify_seed=None):
+        """verify_batches' verdicts for every row against the tree as it is now; only the verdict bytes leave the device."""
+        ok = np.zeros(self.rows, np.uint8)
+        seed = _u8(np.frombuffer(verify_seed, np.uint8)) if verify_seed is not None else None   # None: the library draws one from the OS
+        _chk(lib().dapol_batch_store_verify(self.h, _ptr(seed), _ptr(ok) if ok.shape[0] else None))
         return ok
 
 

@@ -26,6 +26,7 @@
 #include "kernels_compact_paths.h"
 #include "kernels_batches.h"
 #include "kernels_reprove_batches.h"
+#include "kernels_batch_store.h"
 
 using namespace dapol;
 
@@ -492,4 +493,5 @@ int32_t dapol_commit_hash_batch(dapol_ctx* ctx, size_t n, const uint64_t* v, con
 #include "host_batch.inc"
 #include "host_batches.inc"
 #include "host_reprove_batches.inc"
+#include "host_batch_store.inc"
 #include "host_comm.inc"

@@ -197,25 +197,27 @@ int32_t dapol_prove_batches(dapol_ctx* ctx, dapol_tree* tree, size_t nb, const u
     return DAPOL_OK;
 }
 
-int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx, const uint8_t* leaf_C32,
-                             const uint8_t* leaf_H32, const uint64_t* sib_off, const uint8_t* sib_C32, const uint8_t* sib_H32, const uint8_t root_C32[32],
-                             const uint8_t root_H32[32], int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint64_t* range_off,
-                             const uint8_t* range_proofs, const uint8_t verify_seed32[32], uint8_t* ok) {
-    WIRE_SCOPE();
-    if (!ctx || !batch_off || !sib_off || !range_off || !root_C32 || !root_H32 || (nb && !ok)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    VERIFY_SEED_OR_OS(verify_seed32)
-    if (height < 0 || height > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
-    NEEDS_32_BYTE_DIGEST(ctx, "dapol_verify_batches");
-    RCCHK(batches_offsets_ok(nb, batch_off));
-    for (size_t j = 0; j < nb; j++)
-        if (sib_off[j + 1] < sib_off[j] || range_off[j + 1] < range_off[j]) return fail(DAPOL_ERR_INVALID_ARGUMENT, "sib_off and range_off must not decrease");
-    const size_t K = (size_t)batch_off[nb], Tc = nb ? (size_t)(sib_off[nb] - sib_off[0]) : 0, Rc = nb ? (size_t)(range_off[nb] - range_off[0]) : 0;
-    if ((K && (!leaf_idx || !leaf_C32 || !leaf_H32)) || (Tc && (!sib_C32 || !sib_H32)) || (Rc && !range_proofs)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
-    for (size_t j = 0; j < nb; j++) ok[j] = 0;
-    if (nb == 0) return DAPOL_OK;
+// dapol_verify_batches as the host plans it (nb > 0, offsets validated): which batches are well-formed, their S-groups, the merge
+// operations level by level over an arena of K leaf slots, Tc sibling slots and the merged nodes, and the moves into group order.
+// range_proofs is read only where a malformed batch leaves the blobs behind it off the 16-byte grid (`staged`).
+struct VerifyBatchesPlan {
+    BatchesPlan P;
+    BatchesGroups G;
+    size_t K = 0, Tc = 0, Rc = 0, W = 0, T = 0, R = 0, slots = 0, v_words = 8;      // W, T, R: rows, sibling records, range words of the well-formed batches
+    std::vector<BatchesMergeOp> ops;
+    std::vector<size_t> level_end;
+    std::vector<uint32_t> root_slot;
+    std::vector<uint64_t> sibm_dst, sibm_src, rngm_dst, rngm_src;
+    bool aligned = true;
+    std::vector<uint8_t> staged;
+};
+static int32_t verify_batches_plan(dapol_ctx* ctx, int32_t height, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx, const uint64_t* sib_off,
+                                   int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint64_t* range_off, const uint8_t* range_proofs,
+                                   VerifyBatchesPlan& V) {
+    const size_t K = (size_t)batch_off[nb], Tc = (size_t)(sib_off[nb] - sib_off[0]), Rc = (size_t)(range_off[nb] - range_off[0]);
     // Batch by batch what dapol_verify_batch_checked decides before it touches the GPU: a batch whose counts are not those of its
     // leaves is an invalid proof (no row of any group); bad leaf indexes, or more parties than the context has, end the call.
-    BatchesPlan P;
+    BatchesPlan& P = V.P;
     std::vector<uint8_t> well(nb, 0);
     std::vector<size_t> S_of(nb, 0);
     {
@@ -244,8 +246,9 @@ int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const ui
             if (well[j]) P.group_of[j] = (uint32_t)(std::lower_bound(P.group_S.begin(), P.group_S.end(), S_of[j]) - P.group_S.begin());
     }
     const size_t ng = P.group_S.size();
-    const BatchesGroups G = batches_groups(P, nb, &well);
-    const size_t W = G.row0[ng], T = G.sib0[ng], R = G.word0[ng];           // rows, sibling records and range words of the well-formed batches
+    V.G = batches_groups(P, nb, &well);
+    const BatchesGroups& G = V.G;
+    const size_t W = G.row0[ng], T = G.sib0[ng], R = G.word0[ng];
     // Arena slots: the caller's leaves [0, K), the caller's siblings [K, K + Tc), then the merged nodes.  The operations of all
     // well-formed batches, level by level.
     size_t merges = 0;
@@ -253,7 +256,14 @@ int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const ui
         if (well[j]) merges += (size_t)(batch_off[j + 1] - batch_off[j]) * (size_t)height;      // (an upper bound: one merge per leaf and level)
     if ((uint64_t)K + Tc + merges >= 0xffffffffull) return fail(DAPOL_ERR_INVALID_ARGUMENT, "too many nodes in one call (leaves x height must stay below 2^32)");
     std::vector<std::vector<BatchesMergeOp>> level_ops((size_t)height);
-    std::vector<uint32_t> root_slot(nb, 0xffffffffu);
+    std::vector<BatchesMergeOp>& ops = V.ops;
+    std::vector<size_t>& level_end = V.level_end;
+    std::vector<uint32_t>& root_slot = V.root_slot;
+    std::vector<uint64_t>&sibm_dst = V.sibm_dst, &sibm_src = V.sibm_src, &rngm_dst = V.rngm_dst, &rngm_src = V.rngm_src;
+    bool& aligned = V.aligned;
+    std::vector<uint8_t>& staged = V.staged;
+    ops.clear(); level_end.clear();
+    root_slot.assign(nb, 0xffffffffu);
     uint32_t next_slot = (uint32_t)(K + Tc);
     for (size_t j = 0; j < nb; j++) {
         if (!well[j]) continue;
@@ -261,17 +271,15 @@ int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const ui
                                             (uint32_t)batch_off[j], (uint32_t)(K + (sib_off[j] - sib_off[0])), next_slot,
                                             [&](int L, uint32_t left, uint32_t right, uint32_t dst) { level_ops[L].push_back({left, right, dst, (uint32_t)j}); });
     }
-    std::vector<BatchesMergeOp> ops;
-    std::vector<size_t> level_end;
     for (auto& lv : level_ops) { ops.insert(ops.end(), lv.begin(), lv.end()); level_end.push_back(ops.size()); }
     // The moves into group order: row r = the r-th well-formed batch in (group, caller) order.  A malformed batch may leave the blobs
     // behind it at any byte offset; the pieces are 16 bytes, so such a call stages its well-formed blobs on the host first.
     const uint8_t* rbase = range_proofs ? range_proofs + range_off[0] : nullptr;
-    bool aligned = true;
+    aligned = true;
     for (size_t j = 0; j < nb; j++)
         if (well[j] && (range_off[j] - range_off[0]) % 16) aligned = false;
-    std::vector<uint8_t> staged;
-    std::vector<uint64_t> sibm_dst(W + 1, 0), sibm_src(W, 0), rngm_dst(W + 1, 0), rngm_src(W, 0);
+    staged.clear();
+    sibm_dst.assign(W + 1, 0); sibm_src.assign(W, 0); rngm_dst.assign(W + 1, 0); rngm_src.assign(W, 0);
     size_t staged_at = 0;
     if (!aligned) staged.resize(R * 4);
     for (size_t j = 0; j < nb; j++) {
@@ -290,23 +298,93 @@ int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const ui
             sibm_dst[r + 1] = sibm_dst[r] + P.group_S[g];
             rngm_dst[r + 1] = rngm_dst[r] + P.shape[g].words / 4;
         }
-    size_t v_words = 8;                                                       // verify_policy_device's [rows][max m][8] scratch, the largest group's
-    for (size_t g = 0; g < ng; g++) v_words = std::max(v_words, (G.row0[g + 1] - G.row0[g]) * (size_t)P.shape[g].max_m * 8);
+    V.v_words = 8;                                                            // verify_policy_device's [rows][max m][8] scratch, the largest group's
+    for (size_t g = 0; g < ng; g++) V.v_words = std::max(V.v_words, (G.row0[g + 1] - G.row0[g]) * (size_t)P.shape[g].max_m * 8);
+    V.K = K; V.Tc = Tc; V.Rc = Rc; V.W = W; V.T = T; V.R = R; V.slots = next_slot;
+    return DAPOL_OK;
+}
 
-    HIPCHK(hipSetDevice(ctx->device));
+// The device core of dapol_verify_batches over an arena that is ON THE DEVICE already: aC / aH [V.slots + 1][8] words hold the leaves'
+// commitments and hashes in slots [0, K) and the siblings in [K, K + Tc), the merged nodes are written behind them; dR = the range
+// bytes (the caller's, or V.staged where the plan staged them), droot = the root's C [8] then H [8], dseed [8]; d_ok [nb] receives the
+// verdicts.  Everything runs on the context's stream; the caller drains it before its buffers go.
+static int32_t verify_batches_device(dapol_ctx* ctx, const VerifyBatchesPlan& V, size_t nb, int32_t n_bits, uint32_t* aC, uint32_t* aH, const uint32_t* dR,
+                                     const uint32_t* droot, const uint32_t* dseed, uint8_t* d_ok) {
+    const BatchesPlan& P = V.P;
+    const BatchesGroups& G = V.G;
+    const size_t ng = P.group_S.size(), W = V.W, T = V.T, R = V.R;
+    const std::vector<BatchesMergeOp>& ops = V.ops;
+    const std::vector<size_t>& level_end = V.level_end;
     hipStream_t st = ctx->stream;
-    const size_t slots = next_slot, up_bytes = aligned ? Rc : staged.size();
-    DevBuf<uint32_t> aC, aH, droot, dseed, dR, gPC, gR, dV, droot_slot, dpos;
+    DevBuf<uint32_t> gPC, gR, dV, droot_slot, dpos;
     DevBuf<BatchesMergeOp> dops;
-    DevBuf<uint8_t> bad, rok, dsub, dok;
+    DevBuf<uint8_t> bad, rok, dsub;
     DevBuf<uint64_t> dsibm_dst, dsibm_src, drngm_dst, drngm_src;
     StreamDrain drain{st};
-    HIPCHK(aC.alloc(slots * 8 + 8)); HIPCHK(aH.alloc(slots * 8 + 8)); HIPCHK(droot.alloc(16)); HIPCHK(dseed.alloc(8)); HIPCHK(dR.alloc(up_bytes / 4 + 8));
-    HIPCHK(gPC.alloc(T * 8 + 8)); HIPCHK(gR.alloc(R + 8)); HIPCHK(dV.alloc(v_words)); HIPCHK(droot_slot.alloc(nb)); HIPCHK(dpos.alloc(nb));
-    HIPCHK(dops.alloc(ops.size() + 1)); HIPCHK(bad.alloc(nb)); HIPCHK(rok.alloc(W + 1)); HIPCHK(dsub.alloc(W + 1)); HIPCHK(dok.alloc(nb));
+    HIPCHK(gPC.alloc(T * 8 + 8)); HIPCHK(gR.alloc(R + 8)); HIPCHK(dV.alloc(V.v_words)); HIPCHK(droot_slot.alloc(nb)); HIPCHK(dpos.alloc(nb));
+    HIPCHK(dops.alloc(ops.size() + 1)); HIPCHK(bad.alloc(nb)); HIPCHK(rok.alloc(W + 1)); HIPCHK(dsub.alloc(W + 1));
     HIPCHK(dsibm_dst.alloc(W + 1)); HIPCHK(dsibm_src.alloc(W + 1)); HIPCHK(drngm_dst.alloc(W + 1)); HIPCHK(drngm_src.alloc(W + 1));
     HIPCHK(hipMemsetAsync(bad.p, 0, nb, st));
     HIPCHK(hipMemsetAsync(rok.p, 1, W + 1, st));
+    if (!ops.empty()) HIPCHK(hipMemcpyAsync(dops.p, ops.data(), ops.size() * sizeof(BatchesMergeOp), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(droot_slot.p, V.root_slot.data(), nb * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dpos.p, G.pos.data(), nb * 4, hipMemcpyHostToDevice, st));
+    if (W) {
+        HIPCHK(hipMemcpyAsync(dsibm_dst.p, V.sibm_dst.data(), (W + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dsibm_src.p, V.sibm_src.data(), W * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(drngm_dst.p, V.rngm_dst.data(), (W + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(drngm_src.p, V.rngm_src.data(), W * 8, hipMemcpyHostToDevice, st));
+    }
+    size_t done = 0;
+    for (size_t lv = 0; lv < level_end.size(); lv++) {                         // one launch per level over ALL batches
+        const size_t n = level_end[lv] - done;
+        if (!n) continue;
+        LAUNCH_DX(ctx->tv.digest, (k_batches_merge<DX>), dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, n, dops.p + done, aC, aH, bad.p);
+        LAUNCH_CHECK();
+        done = level_end[lv];
+    }
+    RCCHK(batches_move(st, T, W, 2, dsibm_dst.p, dsibm_src.p, aC, gPC.p));
+    RCCHK(batches_move(st, R / 4, W, 1, drngm_dst.p, drngm_src.p, dR, gR.p));
+    for (size_t g = 0; g < ng; g++) {                                          // one policy check per S-group
+        const size_t rows = G.row0[g + 1] - G.row0[g];
+        if (!rows) continue;
+        RCCHK(verify_policy_device(ctx, P.shape[g].plan, rows, (int)P.group_S[g], gPC.p + G.sib0[g] * 8, gR.p + G.word0[g], P.shape[g].words, n_bits, dseed,
+                                   rok.p + G.row0[g], dsub.p + G.row0[g], dV.p));
+    }
+    hipLaunchKernelGGL(k_batches_roots, dim3(nblk(nb, 256)), dim3(256), 0, st, nb, droot_slot.p, dpos.p, aC, aH, droot, bad.p, rok.p, d_ok);
+    LAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(st));
+    return DAPOL_OK;
+}
+
+int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx, const uint8_t* leaf_C32,
+                             const uint8_t* leaf_H32, const uint64_t* sib_off, const uint8_t* sib_C32, const uint8_t* sib_H32, const uint8_t root_C32[32],
+                             const uint8_t root_H32[32], int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint64_t* range_off,
+                             const uint8_t* range_proofs, const uint8_t verify_seed32[32], uint8_t* ok) {
+    WIRE_SCOPE();
+    if (!ctx || !batch_off || !sib_off || !range_off || !root_C32 || !root_H32 || (nb && !ok)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    VERIFY_SEED_OR_OS(verify_seed32)
+    if (height < 0 || height > 64) return fail(DAPOL_ERR_TREE_HEIGHT_TOO_BIG, "tree height must not exceed 64");
+    NEEDS_32_BYTE_DIGEST(ctx, "dapol_verify_batches");
+    RCCHK(batches_offsets_ok(nb, batch_off));
+    for (size_t j = 0; j < nb; j++)
+        if (sib_off[j + 1] < sib_off[j] || range_off[j + 1] < range_off[j]) return fail(DAPOL_ERR_INVALID_ARGUMENT, "sib_off and range_off must not decrease");
+    const size_t K = (size_t)batch_off[nb], Tc = nb ? (size_t)(sib_off[nb] - sib_off[0]) : 0, Rc = nb ? (size_t)(range_off[nb] - range_off[0]) : 0;
+    if ((K && (!leaf_idx || !leaf_C32 || !leaf_H32)) || (Tc && (!sib_C32 || !sib_H32)) || (Rc && !range_proofs)) return fail(DAPOL_ERR_INVALID_ARGUMENT, "null argument");
+    for (size_t j = 0; j < nb; j++) ok[j] = 0;
+    if (nb == 0) return DAPOL_OK;
+    VerifyBatchesPlan V;
+    RCCHK(verify_batches_plan(ctx, height, nb, batch_off, leaf_idx, sib_off, policy, aggregation_factor, n_bits, range_off, range_proofs, V));
+    // the upload / download shell: the caller's leaves, siblings, blobs, root and seed go up into the arena, only ok[nb] comes back
+    const uint8_t* rbase = range_proofs ? range_proofs + range_off[0] : nullptr;
+    const size_t up_bytes = V.aligned ? Rc : V.staged.size();
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevBuf<uint32_t> aC, aH, droot, dseed, dR;
+    DevBuf<uint8_t> dok;
+    StreamDrain drain{st};
+    HIPCHK(aC.alloc(V.slots * 8 + 8)); HIPCHK(aH.alloc(V.slots * 8 + 8)); HIPCHK(droot.alloc(16)); HIPCHK(dseed.alloc(8)); HIPCHK(dR.alloc(up_bytes / 4 + 8));
+    HIPCHK(dok.alloc(nb));
     if (K) {
         HIPCHK(hipMemcpyAsync(aC.p, leaf_C32, K * 32, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(aH.p, leaf_H32, K * 32, hipMemcpyHostToDevice, st));
@@ -315,37 +393,11 @@ int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const ui
         HIPCHK(hipMemcpyAsync(aC.p + K * 8, sib_C32 + sib_off[0] * 32, Tc * 32, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(aH.p + K * 8, sib_H32 + sib_off[0] * 32, Tc * 32, hipMemcpyHostToDevice, st));
     }
-    if (up_bytes) HIPCHK(hipMemcpyAsync(dR.p, aligned ? rbase : staged.data(), up_bytes, hipMemcpyHostToDevice, st));
-    if (!ops.empty()) HIPCHK(hipMemcpyAsync(dops.p, ops.data(), ops.size() * sizeof(BatchesMergeOp), hipMemcpyHostToDevice, st));
+    if (up_bytes) HIPCHK(hipMemcpyAsync(dR.p, V.aligned ? rbase : V.staged.data(), up_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(droot.p, root_C32, 32, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(droot.p + 8, root_H32, 32, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dseed.p, verify_seed32, 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(droot_slot.p, root_slot.data(), nb * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dpos.p, G.pos.data(), nb * 4, hipMemcpyHostToDevice, st));
-    if (W) {
-        HIPCHK(hipMemcpyAsync(dsibm_dst.p, sibm_dst.data(), (W + 1) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(dsibm_src.p, sibm_src.data(), W * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(drngm_dst.p, rngm_dst.data(), (W + 1) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(drngm_src.p, rngm_src.data(), W * 8, hipMemcpyHostToDevice, st));
-    }
-    size_t done = 0;
-    for (size_t lv = 0; lv < level_end.size(); lv++) {                         // one launch per level over ALL batches
-        const size_t n = level_end[lv] - done;
-        if (!n) continue;
-        LAUNCH_DX(ctx->tv.digest, (k_batches_merge<DX>), dim3(nblk(n, 64)), dim3(64), 0, st, ctx->tv.digest, n, dops.p + done, aC.p, aH.p, bad.p);
-        LAUNCH_CHECK();
-        done = level_end[lv];
-    }
-    RCCHK(batches_move(st, T, W, 2, dsibm_dst.p, dsibm_src.p, aC.p, gPC.p));
-    RCCHK(batches_move(st, R / 4, W, 1, drngm_dst.p, drngm_src.p, dR.p, gR.p));
-    for (size_t g = 0; g < ng; g++) {                                          // one policy check per S-group
-        const size_t rows = G.row0[g + 1] - G.row0[g];
-        if (!rows) continue;
-        RCCHK(verify_policy_device(ctx, P.shape[g].plan, rows, (int)P.group_S[g], gPC.p + G.sib0[g] * 8, gR.p + G.word0[g], P.shape[g].words, n_bits, dseed.p,
-                                   rok.p + G.row0[g], dsub.p + G.row0[g], dV.p));
-    }
-    hipLaunchKernelGGL(k_batches_roots, dim3(nblk(nb, 256)), dim3(256), 0, st, nb, droot_slot.p, dpos.p, aC.p, aH.p, droot.p, bad.p, rok.p, dok.p);
-    LAUNCH_CHECK();
+    RCCHK(verify_batches_device(ctx, V, nb, n_bits, aC.p, aH.p, dR.p, droot.p, dseed.p, dok.p));
     HIPCHK(hipMemcpyAsync(ok, dok.p, nb, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return DAPOL_OK;

@@ -375,6 +375,111 @@ class ProofStore {
     Policy policy_ = Policy::Padding;
 };
 
+// dapol_batch_store: the proofs of Dapol::generate_proof_batches for one list of batches kept on the GPU and re-proved in place after
+// update / insert / remove / apply (Dapol::batch_store makes one).  A row is a batch, in the order of the last refresh.  Move-only; it
+// shares ownership of the tree it was made on, as ProofStore does.
+class BatchProofStore {
+  public:
+    BatchProofStore(BatchProofStore&& o) noexcept { *this = std::move(o); }
+    BatchProofStore& operator=(BatchProofStore&& o) noexcept {
+        if (this != &o) {
+            reset();
+            h_ = o.h_; o.h_ = nullptr;
+            ctx_ = std::move(o.ctx_); tree_ = std::move(o.tree_);
+            height_ = o.height_; aggregation_factor_ = o.aggregation_factor_; policy_ = o.policy_; n_bits_ = o.n_bits_;
+        }
+        return *this;
+    }
+    BatchProofStore(const BatchProofStore&) = delete;
+    BatchProofStore& operator=(const BatchProofStore&) = delete;
+    ~BatchProofStore() { reset(); }
+    struct Refreshed { uint64_t proved = 0, kept = 0, n_calls = 0, moved_rows = 0; };
+    // the list the store holds, for the tree as it is now (after update-only edits)
+    Refreshed refresh() { return refresh_impl(0, nullptr, nullptr); }
+    // another list (none: the store is emptied); a batch whose leaves equal an old row's continues that row.  None when there is no
+    // liability at one of the leaves: the store is then as it was.
+    std::optional<Refreshed> refresh(const std::vector<std::vector<uint64_t>>& batches) {
+        std::vector<uint64_t> boff{0}, idx;
+        for (auto& b : batches) { idx.insert(idx.end(), b.begin(), b.end()); boff.push_back(idx.size()); }
+        idx.push_back(0);                                             // (never NULL)
+        Refreshed r;
+        int32_t rc = dapol_batch_store_refresh(h_, batches.size(), boff.data(), idx.data(), &r.proved, &r.kept, &r.n_calls, &r.moved_rows);
+        if (rc == DAPOL_ERR_UNKNOWN_LEAF) return std::nullopt;
+        check(rc);
+        return r;
+    }
+    size_t rows() const { return dapol_batch_store_rows(h_); }
+    std::vector<std::vector<uint64_t>> batches() const {
+        const size_t n = rows();
+        std::vector<uint64_t> boff(n + 1);
+        check(dapol_batch_store_layout(h_, boff.data(), nullptr, nullptr, nullptr));
+        std::vector<uint64_t> idx(boff[n] + 1);
+        check(dapol_batch_store_layout(h_, nullptr, idx.data(), nullptr, nullptr));
+        std::vector<std::vector<uint64_t>> out(n);
+        for (size_t j = 0; j < n; j++) out[j].assign(idx.begin() + boff[j], idx.begin() + boff[j + 1]);
+        return out;
+    }
+    // The stored proofs of the given rows, in any order, duplicates allowed (dapol_batch_store_fetch).
+    std::vector<DapolBatchProof> proofs(const std::vector<uint64_t>& rows_wanted) const {
+        const size_t n = rows(), k = rows_wanted.size();
+        std::vector<uint64_t> boff(n + 1), soff(n + 1), roff(n + 1);
+        check(dapol_batch_store_layout(h_, boff.data(), nullptr, soff.data(), roff.data()));
+        std::vector<uint64_t> idx(boff[n] + 1);
+        check(dapol_batch_store_layout(h_, nullptr, idx.data(), nullptr, nullptr));
+        size_t T = 0, R = 0;
+        for (uint64_t r : rows_wanted) {
+            if (r >= n) throw DapolError(DAPOL_ERR_INVALID_ARGUMENT);
+            T += soff[r + 1] - soff[r]; R += roff[r + 1] - roff[r];
+        }
+        std::vector<uint8_t> C(T * 32 + 1), H(T * 32 + 1), blob(R + 1);
+        check(dapol_batch_store_fetch(h_, k, rows_wanted.data(), C.data(), H.data(), blob.data()));
+        std::vector<DapolBatchProof> out(k);
+        size_t s0 = 0, r0 = 0;
+        for (size_t i = 0; i < k; i++) {
+            const size_t r = rows_wanted[i], S = soff[r + 1] - soff[r], B = roff[r + 1] - roff[r];
+            DapolBatchProof& p = out[i];
+            p.leaf_indexes.assign(idx.begin() + boff[r], idx.begin() + boff[r + 1]);
+            p.merkle_siblings.resize(S);
+            for (size_t s = 0; s < S; s++) {
+                std::memcpy(p.merkle_siblings[s].com.data(), &C[(s0 + s) * 32], 32);
+                std::memcpy(p.merkle_siblings[s].hash.data(), &H[(s0 + s) * 32], 32);
+            }
+            p.range_proofs.assign(blob.begin() + r0, blob.begin() + r0 + B);
+            p.policy = policy_; p.aggregation_factor = aggregation_factor_; p.n_bits = n_bits_; p.height = height_;
+            s0 += S; r0 += B;
+        }
+        return out;
+    }
+    DapolBatchProof proof(uint64_t row) const { return std::move(proofs({row})[0]); }
+    // DapolBatchProof::verify_batch of every row against the tree as it is now, on the device (dapol_batch_store_verify).
+    std::vector<bool> verdicts() const {
+        const size_t n = rows();
+        std::vector<uint8_t> ok(n + 1, 0);
+        check(dapol_batch_store_verify(h_, nullptr, ok.data()));
+        return std::vector<bool>(ok.begin(), ok.begin() + n);
+    }
+    // true when the store is not empty and every row verifies
+    bool verify() const {
+        const auto ok = verdicts();
+        return !ok.empty() && std::all_of(ok.begin(), ok.end(), [](bool x) { return x; });
+    }
+  private:
+    friend class Dapol;
+    BatchProofStore() = default;
+    void reset() { if (h_) dapol_batch_store_destroy(h_); h_ = nullptr; tree_.reset(); ctx_.reset(); }
+    Refreshed refresh_impl(size_t nb, const uint64_t* boff, const uint64_t* idx) {
+        Refreshed r;
+        check(dapol_batch_store_refresh(h_, nb, boff, idx, &r.proved, &r.kept, &r.n_calls, &r.moved_rows));
+        return r;
+    }
+    dapol_batch_store* h_ = nullptr;
+    std::shared_ptr<Context> ctx_;
+    std::shared_ptr<dapol_tree> tree_;
+    int height_ = 0, n_bits_ = 64;
+    size_t aggregation_factor_ = 0;
+    Policy policy_ = Policy::Padding;
+};
+
 // Dapol<D, R> (src/dapol/mod.rs:78-83)
 class Dapol {
   public:
@@ -748,6 +853,15 @@ class Dapol {
     ProofStore proof_store(const Bytes32& nonce_seed, int n_bits = 64) const {
         ProofStore st;
         check(dapol_proof_store_create(ctx_->get(), tree_.get(), (int)policy_, (int)aggregation_factor_, n_bits, nonce_seed.data(), &st.h_));
+        st.ctx_ = ctx_; st.tree_ = tree_;
+        st.height_ = height_; st.aggregation_factor_ = aggregation_factor_; st.policy_ = policy_; st.n_bits_ = n_bits;
+        return st;
+    }
+    // An empty device-resident store of this tree's batch proofs under nonce_seed (dapol_batch_store_create): refresh(batches) fills it,
+    // refresh() brings it up to date after edits, proof(row) serves from it.  The tree must have been built.
+    BatchProofStore batch_store(const Bytes32& nonce_seed, int n_bits = 64) const {
+        BatchProofStore st;
+        check(dapol_batch_store_create(ctx_->get(), tree_.get(), (int)policy_, (int)aggregation_factor_, n_bits, nonce_seed.data(), &st.h_));
         st.ctx_ = ctx_; st.tree_ = tree_;
         st.height_ = height_; st.aggregation_factor_ = aggregation_factor_; st.policy_ = policy_; st.n_bits_ = n_bits;
         return st;

@@ -713,8 +713,8 @@ int32_t dapol_verify_batches(dapol_ctx* ctx, int32_t height, size_t nb, const ui
  * sum-of-m ratio is 2.8-7.7), splitting / 24 0.34 / 0.61 -> 0.07-0.15 s (x3.6-7.1 of 2.5-7.5), padding / 0 0.26 / 0.47 -> 0.02-0.13 s
  * (x3.3-13 of 2.9-118).  Padding with the factor at the smallest sibling count of the call (51; next to nothing is kept) still ran
  * in 0.18 s against 0.42 s, because all of its 64-party proofs are one call here and twelve S-groups there.
- *   Left out: a device-resident store for batch proofs, shard trees and the records route, 64-byte digests, tape mode (DESIGN.md
- * section 9). */
+ *   Left out: shard trees and the records route, 64-byte digests, tape mode.  The old siblings and blobs cross
+ * the bus in both directions on every call; dapol_batch_store below keeps them on the device. */
 int32_t dapol_reprove_batches_plan(int32_t height, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx, const uint8_t* has_old,
                                    size_t k, const uint64_t* edited_idx, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
                                    uint64_t* n_proved, uint64_t* total_proved, uint64_t* sum_m_proved, uint64_t* sum_m_all);
@@ -722,6 +722,70 @@ int32_t dapol_reprove_batches(dapol_ctx* ctx, dapol_tree* tree, size_t nb, const
                               int32_t policy, int32_t aggregation_factor, int32_t n_bits, const uint8_t nonce_seed32[32],
                               const uint8_t* has_old, const uint8_t* old_sib_C32, const uint8_t* old_range, uint8_t* sib_C32,
                               uint8_t* sib_H32, uint8_t* range_out, uint64_t* proved_out, uint64_t* kept_out, uint64_t* n_calls_out);
+
+/* A BATCH STORE keeps what dapol_prove_batches issues for one batch list -- under one (context, tree, policy, aggregation factor, n_bits,
+ * nonce seed) -- in device memory between calls: what dapol_proof_store is to single-leaf proofs.  A ROW is a batch; rows are in the
+ * caller's order of the last successful refresh.  The store keeps, at dapol_batches_plan's offsets, the leaf lists, the sibling
+ * commitments [sib_off[rows]][32], the sibling hashes and the blobs (range_off[rows] bytes) on the device, and a copy of batch_off /
+ * leaf_idx on the host.  After an edit of the tree a refresh re-proves what dapol_reprove_batches would re-prove, with the old data
+ * where the last refresh left it: no old array goes up and no blob comes down; a caller fetches the rows it serves.
+ *   Ownership.  As dapol_proof_store: the store retains its context and is counted by its tree (the same counter: dapol_tree_destroy
+ * on a tree with a live store returns DAPOL_ERR_INVALID_ARGUMENT and destroys nothing).  The tree may be edited freely between calls;
+ * the store reads it only inside its own calls, on the context's stream.  Every call below except _destroy and _rows refuses
+ * (DAPOL_ERR_INVALID_ARGUMENT, nothing written) a NULL store, a tree marked invalid, a store marked unusable, and a dapol_wire_config
+ * whose siblings_leaf_first differs from the value recorded at creation.
+ *   dapol_batch_store_create: an empty store (0 rows).  Refuses what dapol_reprove_batches refuses for the same context and tree, with
+ * its codes: NULL arguments, a tree of another context, a shard tree, a 64-byte digest (DAPOL_ERR_INVALID_DIGEST_SIZE).  What depends
+ * on a batch (aggregation_factor, n_bits, the parties) is refused by the refresh that brings the batch.  *store is written only on success.
+ *   dapol_batch_store_destroy: overwrites the seed on the device, frees everything, releases the context.  NULL is DAPOL_OK.
+ *   dapol_batch_store_refresh: afterwards _read(0, rows) equals, byte for byte (siblings C, siblings H, blobs), what dapol_prove_batches
+ * returns for the store's list on the tree as it is now under the store's seed, policy, factor and n_bits.  batch_off = NULL with
+ * nb = 0: the list the store already holds (every update-only edit); a non-NULL batch_off replaces the list, with nb = 0 it empties
+ * the store.  CONTINUATION: new batch j continues an old row when their leaf lists are equal, in length and in every index; of several
+ * equal old rows the lowest (equal lists have equal bytes under one seed -- the seed chains through the leaves -- so the choice cannot
+ * be observed); a batch with no equal old row has no old proof.  *proved, *kept and *n_calls are dapol_reprove_batches' for the new
+ * list with the store's previous rows as the old data and has_old = the continuation; *moved_rows = old rows copied into new buffers.
+ * Each of the four may be NULL.  IN PLACE, when the list is unchanged (NULL, or equal to the stored list row for row): nothing moves
+ * (*moved_rows = 0), the new siblings are gathered into the store's spare sibling arrays and compared with the ones in use, the dirty
+ * pieces are written into the blobs where they lie, the arrays swap; the plan tables are on the device already, so nothing is
+ * uploaded.  MOVING, in every other case: new buffers are allocated at the new offsets, continued rows are copied into them (blobs,
+ * and the old commitments to compare against), everything else is proved fresh, the old buffers are freed after the copy.  All or
+ * nothing: a bad list and an aggregation_factor above some batch's sibling count (dapol_prove_batches' refusals, with its codes, its
+ * "batch <j>:" messages and its precedence), a leaf the tree does not hold (DAPOL_ERR_UNKNOWN_LEAF) and a failed allocation leave the
+ * store byte for byte as it was.  A stored batch whose leaf has been removed meets the unknown-leaf case on a NULL-list refresh: pass
+ * the list without that batch.  A HIP failure after the first write of an in-place refresh marks the store unusable: destroy it and
+ * create it again.
+ *   dapol_batch_store_rows: the row count; 0 for NULL.
+ *   dapol_batch_store_layout: the host copy of the list and dapol_batches_plan's offsets for it: batch_off [rows + 1], leaf_idx
+ * [batch_off[rows]], sib_off [rows + 1] (records), range_off [rows + 1] (bytes).  Each output may be NULL.
+ *   dapol_batch_store_fetch: k row numbers, in any order, duplicates allowed; the rows are gathered on the device into one staging
+ * buffer in the layout dapol_batches_plan gives for those batches in query order, and copied back from there.  A row number >= rows
+ * -> DAPOL_ERR_INVALID_ARGUMENT with nothing written.  Output pointers may be NULL.  k = 0 does nothing.
+ *   dapol_batch_store_read: rows [first, first + count) by plain copies; refused when first + count exceeds the rows.  Output pointers
+ * may be NULL.
+ *   dapol_batch_store_verify: ok[rows] = what dapol_verify_batches returns for the rows read back, with the leaves' commitments and
+ * hashes taken from level 0 of the tree as it is now and the root from its top level -- so in a store that has not been refreshed
+ * since an edit every batch with a sibling above an edited leaf fails (a batch that holds the edited leaf itself stays valid).  Only
+ * ok crosses the bus.  verify_seed32 = NULL draws one.  A stored leaf that the tree no longer holds -> DAPOL_ERR_UNKNOWN_LEAF,
+ * nothing written.
+ *   When to use it (tools/bench_batch_store.py): whenever batch proofs are served after edits and the caller
+ * does not need every blob back after every edit.  2^16 leaves at height 32, 4,096 batches of 2 / 4 random leaves, 64-bit proofs, one
+ * MI355X, 1 to 4,096 replaced liabilities, refresh + fetch of 256 rows against the whole dapol_reprove_batches call on the same edited
+ * tree: the gain is the bus trip, 6-20 ms a call -- padding / 16 0.067-0.142 -> 0.059-0.122 s (x1.10-1.29), splitting / 24 0.070-0.148
+ * -> 0.064-0.132 s (x1.07-1.20), padding / 0 0.018-0.129 -> 0.010-0.109 s (x1.14-2.5); refresh + read of everything x1.05-1.55.
+ *   Left out: shard trees, 64-byte digests, tape mode, persistence (a store lives and dies with its process), compact forms (DESIGN.md
+ * section 9). */
+typedef struct dapol_batch_store dapol_batch_store;
+int32_t dapol_batch_store_create(dapol_ctx* ctx, dapol_tree* tree, int32_t policy, int32_t aggregation_factor, int32_t n_bits,
+                                 const uint8_t nonce_seed32[32], dapol_batch_store** store);
+int32_t dapol_batch_store_destroy(dapol_batch_store* store);
+int32_t dapol_batch_store_refresh(dapol_batch_store* store, size_t nb, const uint64_t* batch_off, const uint64_t* leaf_idx, uint64_t* proved,
+                                  uint64_t* kept, uint64_t* n_calls, uint64_t* moved_rows);
+size_t dapol_batch_store_rows(dapol_batch_store* store);
+int32_t dapol_batch_store_layout(dapol_batch_store* store, uint64_t* batch_off, uint64_t* leaf_idx, uint64_t* sib_off, uint64_t* range_off);
+int32_t dapol_batch_store_fetch(dapol_batch_store* store, size_t k, const uint64_t* row, uint8_t* sib_C32, uint8_t* sib_H32, uint8_t* range_out);
+int32_t dapol_batch_store_read(dapol_batch_store* store, size_t first, size_t count, uint8_t* sib_C32, uint8_t* sib_H32, uint8_t* range_out);
+int32_t dapol_batch_store_verify(dapol_batch_store* store, const uint8_t verify_seed32[32], uint8_t* ok);
 
 /* SHARED sub-proofs on the verifier's side -- the counterpart of dapol_prove_entities_shared: a call that checks many entities'
  * proofs (an exchange before it publishes them, an auditor who checks everyone's) verifies every run of equal sub-proofs once.
